@@ -1,7 +1,20 @@
 """Benchmark: ForwardTacotron.generate() mel-frames/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU)
+
+A plain run sets up, runs W warm-up steps, times K steps, and prints one JSON line whose
+figures (`value`, `ms_per_step`, `valid_frames_per_s`) come from those K steps alone.
+  --dump-outputs DIR     after the timed steps, write what the last of them returned (the
+                         dict generate() gives its caller: mel, mel_post, dur, pitch, energy;
+                         wavernn: wav) as DIR/<name>.npy, float32 (integers and float64:
+                         float64), at most 64 MB together (a fixed seeded sample of an array
+                         that is larger than its share).  Tokens and weights are seeded, so
+                         the same arguments give the same inputs in every run and build.
+  --full                 then run every further measurement and add it to the line: the
+                         roofline of the dominant kernel, host_to_host, prenet_bank,
+                         collectives (N > 1), with_vocoder, cpu_baseline and parity, listed
+                         below; --kernels and --vocoder need it.
 
 Workload (default: BASELINE.json configs[2], "c3"): ForwardTacotron LJSpeech config, batch =
 64 synthetic phoneme sequences per GPU (lengths U{50..200}, ids U{1..134}, pad 0; seed =
@@ -34,10 +47,11 @@ only (result collection) — the reference's output for the global batch (weak s
 per-GPU work fixed).  The gather runs on its own communicator and is left in flight while
 the next step runs (--gather-overlap off: blocking).  Barrier + synchronize around the K
 timed steps, max elapsed over ranks, value = frames of the global mel_post / that time.
-`collectives` in the line: per-collective RCCL times (HIP events, max over ranks) from one
-more loop with the gather blocking, the weights broadcast, and every rank's step time.
+`collectives` in the --full line: per-collective RCCL times (HIP events, max over ranks)
+from one more loop with the gather blocking, the weights broadcast, and every rank's step
+time.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     the dominant kernel (largest device time inside the timed steps, measured
                with HIP events on the launch stream): algorithmic FLOPs per launch / its
                average duration, against the peak of the arithmetic that kernel issues
@@ -254,6 +268,71 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET = 64 * 10 ** 6  # bytes over all files of one --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: tensor or array} as path/<name>.npy.  Floating arrays are
+    written as float32 (float64 stays float64), integer ones as float64 (exact).  When the
+    arrays exceed DUMP_BUDGET together, each one larger than an equal share of it is reduced
+    to a fixed sample: the flattened elements at sorted indices drawn once from PCG64 seeded
+    with the array's size, so two builds given the same arguments write the same elements."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        arrs[name] = a.astype(np.float32 if a.dtype.kind == 'f' and a.dtype != np.float64
+                              else np.float64, copy=False)
+    if sum(a.nbytes for a in arrs.values()) > DUMP_BUDGET:
+        share = DUMP_BUDGET // len(arrs)
+        for name, a in arrs.items():
+            if a.nbytes > share:
+                rng = np.random.Generator(np.random.PCG64([a.size, 64]))
+                idx = np.sort(rng.integers(0, a.size, share // a.itemsize))
+                arrs[name] = a.reshape(-1)[idx]
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def headline(args, world, overlap, x_np, out, frames, elapsed):
+    """The result line of a plain run (every figure from the timed steps alone); --full adds
+    its further measurements to it."""
+    fp = args.model == 'fast_pitch'
+    line = {
+        'metric': 'mel-frames/sec at batch=64 LJSpeech shapes (%s.generate, B*T_mel per s)'
+                  % ('FastPitch' if fp else 'ForwardTacotron'),
+        'value': round(frames / elapsed, 1), 'unit': 'mel-frames/s', 'n_gpus': world,
+        'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'fp32',
+        'data': 'synthetic (seeded LJSpeech-shaped phoneme batches, synthetic weights)',
+        'config': {'workload': (f'{"c5: FastPitch" if fp else ("c2" if args.batch == 1 else "c3") + ": ForwardTacotron"} generate, '
+                                if world == 1 else
+                                f'c4: {"FastPitch" if fp else "ForwardTacotron"} generate of one '
+                                f'global batch sharded over {world} GPUs (global padding, '
+                                f'fill rule and T_mel by RCCL all-reduce, the result gathered to '
+                                f'rank 0{" on its own communicator, pipelined with the next step" if overlap else ""}), ')
+                               + f'batch={args.batch} per GPU, '
+                               f'phoneme lengths U{{{args.tmin}..{args.tmax}}}',
+                   'global_batch': args.batch * world, 'T_phonemes': int(x_np.shape[1]),
+                   'T_mel': int(out['mel_post'].size(2)), 'parallelism': f'dp{world}'},
+        'value_basis': ('tokens resident in HBM when the timed region starts, mel_post left in '
+                        'HBM (PCIe-inclusive rates are never `value`); SURVEY 8(d)\'s per-call '
+                        'figure with the token H2D and the mel_post D2H is `host_to_host` '
+                        '(--full)'),
+    }
+    if world == 1:
+        # valid frames: frames of the non-pad phonemes (the rest of B * T_mel is padding)
+        cnt = ft_oracle_counts(out['dur'].float().cpu().numpy())
+        valid = int((cnt * (x_np != 0)).sum())
+        line['valid_frames_per_step'] = valid
+        line['valid_frames_per_s'] = round(valid * args.steps / elapsed, 1)
+    if args.callbacks != 'identity':
+        line['config']['callbacks'] = (f'gen_forward.py:103-104: pitch_function = lambda x: x * {args.amp}, '
+                                       'energy_function = lambda x: x')
+    return line
+
+
 def dsp_kernel_table(kern):
     """The audio kernels of a probe summary against the HBM roofline: algorithmic bytes per
     launch (each input read once, each output written once) / the launch's average device
@@ -302,7 +381,16 @@ def main():
                          'on with nccl; off in the gloo rehearsal, whose ranks share one GPU)')
     ap.add_argument('--no-host-loop', action='store_true',
                     help='skip the second (host-to-host, PCIe-inclusive) timed loop')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run every further measurement (see the '
+                         'module docstring); a plain run times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if not args.full and (args.kernels or args.vocoder != 'none'):
+        ap.error('--kernels and --vocoder belong to the further measurements: add --full')
     if args.config == 'c2':
         args.batch, args.tmin, args.tmax = 1, 120, 120
     shape = (args.batch, args.tmin, args.tmax)
@@ -406,6 +494,18 @@ def main():
         barrier()
         t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:  # the last timed step's result, before any later call
+        dump_outputs(args.dump_outputs, out)
+    if not args.full:  # a plain run ends here: the line of the timed steps alone
+        if world > 1:
+            t = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t[0].item())
+        if rank == 0:
+            print(json.dumps(headline(args, world, overlap, x_np, out, frames, elapsed)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     kern = probe.summary()
 
     # c4: the communication share.  One more loop of `steps` calls with the blocking
@@ -720,41 +820,8 @@ def main():
                             'note': 'a prior PMC run of this workload, not this run'}
                 if 'planes' in pb:
                     prenet['warm_ms_split_planes'] = round(pb['planes'], 4)
-        value = frames / elapsed
-        # valid frames: frames of the non-pad phonemes (the rest of B * T_mel is padding)
-        tok = (x_np != 0) if world == 1 else None
-        valid = None
-        if tok is not None:
-            cnt = ft_oracle_counts(out['dur'].float().cpu().numpy())
-            valid = int((cnt * tok).sum())
-        fp = args.model == 'fast_pitch'
-        line = {
-            'metric': 'mel-frames/sec at batch=64 LJSpeech shapes (%s.generate, B*T_mel per s)'
-                      % ('FastPitch' if fp else 'ForwardTacotron'),
-            'value': round(value, 1), 'unit': 'mel-frames/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'fp32',
-            'data': 'synthetic (seeded LJSpeech-shaped phoneme batches, synthetic weights)',
-            'config': {'workload': (f'{"c5: FastPitch" if fp else ("c2" if args.batch == 1 else "c3") + ": ForwardTacotron"} generate, '
-                                    if world == 1 else
-                                    f'c4: {"FastPitch" if fp else "ForwardTacotron"} generate of one '
-                                    f'global batch sharded over {world} GPUs (global padding, '
-                                    f'fill rule and T_mel by RCCL all-reduce, the result gathered to '
-                                    f'rank 0{" on its own communicator, pipelined with the next step" if overlap else ""}), ')
-                                   + f'batch={args.batch} per GPU, '
-                                   f'phoneme lengths U{{{args.tmin}..{args.tmax}}}',
-                       'global_batch': args.batch * world, 'T_phonemes': int(x_np.shape[1]),
-                       'T_mel': int(out['mel_post'].size(2)), 'parallelism': f'dp{world}'},
-            'roofline': roof,
-            'value_basis': ('tokens resident in HBM when the timed region starts, mel_post left in '
-                            'HBM: the harness contract (PCIe-inclusive rates are never `value`); '
-                            'SURVEY 8(d)\'s per-call figure with the token H2D and the mel_post '
-                            'D2H is `host_to_host`'),
-        }
-        if valid is not None:
-            line['valid_frames_per_step'] = valid
-            line['valid_frames_per_s'] = round(valid * args.steps / elapsed, 1)
+        line = headline(args, world, overlap, x_np, out, frames, elapsed)
+        line['roofline'] = roof
         if host_elapsed is not None:
             line['host_to_host'] = {
                 'value': round(frames / host_elapsed, 1), 'unit': 'mel-frames/s',
@@ -768,9 +835,6 @@ def main():
                            'ms_per_step': round(host_serial / args.steps * 1e3, 3),
                            'what': 'pageable x.to(dev) + generate() + mel_post.cpu() per call, '
                                    'serialised as gen_forward.py:111-120 writes it'}}
-        if args.callbacks != 'identity':
-            line['config']['callbacks'] = (f'gen_forward.py:103-104: pitch_function = lambda x: x * {args.amp}, '
-                                           'energy_function = lambda x: x')
         if prenet is not None:
             line['prenet_bank'] = prenet
         if world > 1:
@@ -824,6 +888,8 @@ def bench_wavernn(args, world, rank, dev):
         barrier()
         elapsed = time.perf_counter() - t0
     kern = probe.summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'wav': wav})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64,
                          device=dev if dist.get_backend() == 'nccl' else 'cpu')
@@ -864,7 +930,7 @@ def bench_wavernn(args, world, rank, dev):
         'roofline': roof,
         'realtime_factor': round(samples * world / elapsed / cfg['dsp']['sample_rate'], 2),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         line['cpu_baseline'] = cpu_baseline_wavernn(sd, cfg, mels_np, target, overlap, B, L, samples,
                                                     args.steps)
     print(json.dumps(line), flush=True)

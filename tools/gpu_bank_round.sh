@@ -19,5 +19,5 @@ run() {  # name timeout cmd...
 run ${T}_bank_tests 400 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests/test_gpu_kernels.py -k "conv_bank"
 TAILN=40 run ${T}_stamps 200 env SLOWEST=4 FTMI_LIB=$PWD/forwardtacotron_amd/libftmi_stamps.so python -u tools/bank_halves_stamps.py ${@:-img}
 run ${T}_bank_bench 200 python -u tools/bank_bench.py 120 50 halves-image halves
-TAILN=1 run ${T}_c2 300 python -u bench.py --config c2 --callbacks gen_forward --steps 20 --warmup 3 --no-cpu-baseline
+TAILN=1 run ${T}_c2 300 python -u bench.py --full --config c2 --callbacks gen_forward --steps 20 --warmup 3 --no-cpu-baseline
 echo ALLOK

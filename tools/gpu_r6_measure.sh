@@ -18,12 +18,12 @@ step() {  # name timeout cmd...
 }
 MF="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE GRBM_COUNT"
 if [ "$PART" = bench ] || [ "$PART" = all ]; then
-  step bench_c3 400 python bench.py --steps 20 --warmup 3 --kernels
-  step bench_c2 300 python bench.py --config c2 --callbacks gen_forward --steps 20 --warmup 3 --kernels
-  step bench_c2_gl 400 python bench.py --config c2 --callbacks gen_forward --vocoder griffinlim --nnls lbfgsb --vocoder-steps 3 --steps 20 --warmup 3 --no-cpu-baseline
-  step bench_c2_gl_fista 300 python bench.py --config c2 --callbacks gen_forward --vocoder griffinlim --nnls fista --steps 20 --warmup 3 --no-cpu-baseline
-  step bench_c5 500 python bench.py --model fast_pitch --vocoder griffinlim --nnls fista --steps 10 --warmup 3 --kernels
-  step bench_wr 300 python bench.py --model wavernn --steps 3 --warmup 1
+  step bench_c3 400 python bench.py --full --steps 20 --warmup 3 --kernels
+  step bench_c2 300 python bench.py --full --config c2 --callbacks gen_forward --steps 20 --warmup 3 --kernels
+  step bench_c2_gl 400 python bench.py --full --config c2 --callbacks gen_forward --vocoder griffinlim --nnls lbfgsb --vocoder-steps 3 --steps 20 --warmup 3 --no-cpu-baseline
+  step bench_c2_gl_fista 300 python bench.py --full --config c2 --callbacks gen_forward --vocoder griffinlim --nnls fista --steps 20 --warmup 3 --no-cpu-baseline
+  step bench_c5 500 python bench.py --full --model fast_pitch --vocoder griffinlim --nnls fista --steps 10 --warmup 3 --kernels
+  step bench_wr 300 python bench.py --full --model wavernn --steps 3 --warmup 1
 fi
 if [ "$PART" = prof ] || [ "$PART" = all ]; then
   step prof_c3 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-loop
