@@ -30,7 +30,7 @@
 // and a SCALED f16 tail (Ootomo & Yokota, arXiv:2203.03341):
 //   a = a_h + 2^-11 a_t,   a_h = f16(a), a_t = f16((a - a_h) * 2^11)
 // The weights (pre-split once by ftmi_split_weights_f16, per output column n pre-scaled by
-// a power of two s_n so that |w| s_n < 16) are stored as three f16 planes
+// a power of two s_n so that 8 <= max|w| s_n < 16) are stored as three f16 planes
 //   B0 = 2^11 w_h,  B1 = w_t,  B2 = w_h            (w = w_h + 2^-11 w_t after scaling)
 // and one fp32 accumulator collects   a_h B0 + a_h B1 + a_t B2 = 2^11 (a w - 2^-22 a_t w_t),
 // multiplied back by colscale[n] = 2^-11 / s_n (exact) in the epilogue.  The scaled tails
@@ -3063,8 +3063,10 @@ __global__ void split_weights_kernel(const float *__restrict__ w, int64_t N, int
 
 // w [N][K] fp32 -> f16 planes [3][N][Kpad] (B0 = 2^11 w_h, B1 = w_t, B2 = w_h of the
 // column-scaled row w s_n) followed by colscale[N] = 2^-11 / s_n.  One workgroup per row:
-// s_n = 2^-e with the smallest e >= 0 such that max|w[n]| s_n < 16 (so 2^11 w_h stays
-// inside the f16 range).
+// s_n = 2^-e normalises the row, 8 <= max|w[n]| s_n < 16 (e >= -100; an all-zero row: e = 0):
+// 2^11 w_h stays inside the f16 range, and a row of small weights is scaled UP, so its heads
+// and tails are normal f16 numbers (with e >= 0 only, a row below ~2^-17 lost its tails to the
+// f16 subnormal spacing: 7e-5 relative on a 2^-20-sized row).
 // frag: planes in the fragment-major order [N/16][Kpad/32][64 lanes][8] of the
 // v_mfma_f32_16x16x32_f16 B operand (lane = n % 16 + 16 ((k / 8) % 4), element k % 8) —
 // the layout of ftmi_highway_stack; else row-major [N][Kpad].
@@ -3082,9 +3084,9 @@ __global__ __launch_bounds__(256) void split_weights_f16_kernel(const float *__r
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  int ex = 0;
+  int ex = 4;
   if (__builtin_isfinite(m) && m > 0.f) frexpf(m, &ex);  // m = f * 2^ex, f in [0.5, 1)
-  const int e = ex > 4 ? ex - 4 : 0;                     // m * 2^-e < 2^4
+  const int e = ex - 4 > -100 ? ex - 4 : -100;           // 2^3 <= m * 2^-e < 2^4
   const int64_t plane = N * Kpad;
   for (int64_t k = threadIdx.x; k < Kpad; k += 256) {
     const float v = k < K ? ldexpf(row[k], -e) : 0.f;

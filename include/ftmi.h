@@ -166,7 +166,8 @@ int64_t ftmi_split_weights_bytes(int64_t N, int64_t K);
 int ftmi_split_weights(const float *w, int64_t N, int64_t K, void *out, ftmi_stream_t stream);
 
 /* Split fp32 weights [N][K] once for FTMI_MMA_F16X3: per row n a power-of-two scale
- * s_n = 2^-e (smallest e >= 0 with max|w[n]| s_n < 16), h = f16(w s_n),
+ * s_n = 2^-e that normalises the row (8 <= max|w[n]| s_n < 16, e >= -100, which also
+ * scales small rows up into the normal f16 range; an all-zero row: e = 0), h = f16(w s_n),
  * t = f16((w s_n - h) * 2^11); layout: f16 planes [3][N][Kpad] = (2^11 h, t, h), Kpad =
  * roundup(K, 32), zero padded, then float colscale[N] = 2^-11 / s_n.  out must hold
  * ftmi_split_weights_f16_bytes(N, K) bytes (16-byte aligned).  The conv bank's w_split

@@ -59,8 +59,10 @@ def length_regulator(x, dur):
 
 @torch.no_grad()
 def generate(sd: Dict[str, torch.Tensor], x: torch.Tensor, alpha: float = 1.0,
-             heads: int = 2, layers: int = 4) -> Dict[str, torch.Tensor]:
-    """FastPitch.generate + _generate_mel (fast_pitch.py:286-340)."""
+             heads: int = 2, layers: int = 4, lr_dur=None) -> Dict[str, torch.Tensor]:
+    """FastPitch.generate + _generate_mel (fast_pitch.py:286-340).  lr_dur (accuracy tests
+    only): durations the LengthRegulator uses instead of its own (a float64 run fed the
+    fp32 run's, so both follow the same frame counts)."""
     dur = series_predictor(sd, 'dur_pred.', x, alpha=alpha).squeeze(2)
     if torch.sum(dur.long()) <= 0:
         dur.fill_(2.)
@@ -70,7 +72,7 @@ def generate(sd: Dict[str, torch.Tensor], x: torch.Tensor, alpha: float = 1.0,
     h = forward_transformer(sd, 'prenet.', h, heads, layers, kpm=x == 0)
     h = h + F.conv1d(pitch, sd['pitch_proj.weight'], sd['pitch_proj.bias'], padding=1).transpose(1, 2)
     h = h + F.conv1d(energy, sd['energy_proj.weight'], sd['energy_proj.bias'], padding=1).transpose(1, 2)
-    h, dur = length_regulator(h, dur)
+    h, dur = length_regulator(h, dur if lr_dur is None else lr_dur.clone().to(dur.dtype))
     h = forward_transformer(sd, 'postnet.', h, heads, layers)
     mel = F.linear(h, sd['lin.weight'], sd['lin.bias']).transpose(1, 2)
     return {'mel': mel, 'mel_post': mel, 'dur': dur, 'pitch': pitch, 'energy': energy}

@@ -33,10 +33,10 @@ FACTORS = {'default': (1.5, 2.0), 'exact_fp32_mfma': (3.0, 5.0)}  # (mean, max)
 FLOOR = 2e-6
 
 
-def _record(name, stats):
+def _record(name, stats, fname=None):
     out = os.path.join(ROOT, 'gpurun_out')
     os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, f'accuracy_{name}.json'), 'w') as f:
+    with open(os.path.join(out, fname or f'accuracy_{name}.json'), 'w') as f:
         json.dump(stats, f, indent=1)
     print(name, json.dumps(stats))
 

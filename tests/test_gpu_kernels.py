@@ -637,7 +637,8 @@ def test_split_weights_exact(rng):
 
 def test_split_weights_f16_layout(rng):
     """f16x3 planes: B0 = 2^11 h, B2 = h, w s_n ~= h + 2^-11 B1 to 2^-22 relative; the
-    column scale is a power of two with max|w| s_n < 16; K padding is zero."""
+    column scale is a power of two that normalises the row, 8 <= max|w| s_n < 16 (s_n < 1 for
+    a large row, > 1 for a small one, 1 for an all-zero row); K padding is zero."""
     from forwardtacotron_amd import ops
     N, K = 40, 300
     w = rng.normal(0, 1, (N, K)).astype(np.float32)
@@ -648,8 +649,10 @@ def test_split_weights_f16_layout(rng):
     planes = blk[:3 * N * Kp * 2].view(np.float16).reshape(3, N, Kp).astype(np.float64)
     cs = blk[3 * N * Kp * 2:3 * N * Kp * 2 + 4 * N].view(np.float32).astype(np.float64)
     s = 2.0 ** -11 / cs
-    assert np.all(np.log2(s) == np.round(np.log2(s))) and np.all(s <= 1.0)
-    assert np.all(np.abs(w).max(1) * s < 16) and s[3] < 1.0 and s[0] == 1.0
+    assert np.all(np.log2(s) == np.round(np.log2(s)))
+    top = np.abs(w).max(1) * s
+    assert np.all(top < 16) and np.all(top[np.arange(N) != 5] >= 8)
+    assert s[3] < 1.0 and s[0] > 1.0 and s[5] == 1.0
     np.testing.assert_array_equal(planes[0], planes[2] * 2048.0)
     back = (planes[2] + planes[1] / 2048.0) / s[:, None]
     ws = w.astype(np.float64)
