@@ -21,7 +21,7 @@ _lib = None
 
 c_int, c_int64, c_float, c_void_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 P = c_void_p  # every device pointer travels as void*
-ABI_VERSION = 19
+ABI_VERSION = 20
 MMA_F32, MMA_BF16X6, MMA_F16X3 = 0, 1, 2
 
 
@@ -45,6 +45,17 @@ class WaveRNNArgs(ctypes.Structure):
         ('seed', ctypes.c_uint64)] + [(n, c_int) for n in (
             'bias_row', 'item_rows', 'frames_per_item', 'hop', 'fold_stride', 'batched', 'B', 'L',
             'n_classes', 'mol', 'rnn_dims', 'fc_dims', 'feat_dims', 'aux_dims')]
+
+
+class TacoArgs(ctypes.Structure):
+    """Mirror of ftmi_taco_args (include/ftmi.h)."""
+    _fields_ = [(n, P) for n in (
+        'enc', 'enc_proj', 'pre_w1t', 'pre_b1', 'pre_w2t', 'pre_b2', 'gru_wih', 'gru_whh', 'gru_bih',
+        'gru_bhh', 'lsa_conv', 'lsa_L', 'lsa_Lb', 'lsa_wt', 'lsa_Wb', 'lsa_v', 'rin_w', 'rin_b',
+        'l1_wih', 'l1_whh', 'l1_bih', 'l1_bhh', 'l2_wih', 'l2_whh', 'l2_bih', 'l2_bhh', 'mel_w',
+        'pre_gi', 'mel_out', 'attn_out', 'steps_out', 'status', 'workspace', 'stamps')] + [
+        ('stop_threshold', c_float)] + [(n, c_int) for n in (
+            'B', 'T', 'r', 'steps', 'decoder_dims', 'lstm_dims', 'n_mels', 'prenet_dims')]
 
 
 class NnlsArgs(ctypes.Structure):
@@ -129,6 +140,8 @@ SIGNATURES = {
     'ftmi_wavernn': (c_int, [ctypes.POINTER(WaveRNNArgs), P]),
     'ftmi_set_wavernn_spin_limit': (ctypes.c_uint32, [ctypes.c_uint32]),
     'ftmi_wr_unfold': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'ftmi_tacotron_decoder_workspace_bytes': (c_int64, [c_int, c_int]),
+    'ftmi_tacotron_decoder': (c_int, [ctypes.POINTER(TacoArgs), P]),
     'ftmi_mel_nnls': (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P,
                               c_float, c_int, P, P]),
     'ftmi_nnls_lbfgsb_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int, c_int]),

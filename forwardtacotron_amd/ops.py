@@ -976,3 +976,30 @@ def wr_unfold(samples: torch.Tensor, target: int, overlap: int, batched: bool, m
            samples.data_ptr(), B, L, target, overlap, int(batched), int(mu_law), n_classes,
            wave_len, fade_len, out.data_ptr(), _stream())
     return out
+
+
+# ---- Tacotron decoder loop (csrc/tacotron.hip) ---------------------------------------------
+
+TACO_MAX_TOKENS, TACO_MAX_BATCH = 512, 2  # include/ftmi.h FTMI_TACO_MAX_*
+
+
+def tacotron_decoder_workspace(B: int, T: int, device) -> torch.Tensor:
+    n = int(_lib.load().ftmi_tacotron_decoder_workspace_bytes(B, T))
+    if n == 0:
+        raise _lib.FtmiError(
+            f'the Tacotron decoder launch takes 1..{TACO_MAX_TOKENS} tokens and up to '
+            f'{TACO_MAX_BATCH} items per launch (got T={T}, B={B}): FTMI_E_UNSUPPORTED')
+    return torch.empty(n // 4, device=device, dtype=torch.int32)
+
+
+def tacotron_decoder(args, device) -> None:
+    """Enqueue ftmi_tacotron_decoder (args: a filled _lib.TacoArgs; the caller keeps every
+    buffer alive).  The status word pointer is set here."""
+    args.status = status_word(device).data_ptr()
+    mode = 'forward' if args.pre_gi else 'generate'
+    n = (args.steps + args.r - 1) // args.r
+    # per step: the 20 MB of weights' multiply-adds that are live (mel_proj: 80 r rows)
+    flops = 2.0 * args.B * n * (768 * 640 + 256 * 256 + 512 * 512 + 4 * 2048 * 512
+                                + 80 * args.r * 512 + 2 * args.T * 256)
+    launch('ftmi_tacotron_decoder', f'tacotron_decoder[{mode},B={args.B},T={args.T},r={args.r},n={n}]',
+           flops, 4.0 * args.B * n * (80 * args.r + args.T), ctypes.byref(args), _stream())

@@ -23,6 +23,19 @@ WaveRNN vocoder (model='wavernn', models/fatchord_version.py): BatchNorm as abov
 upsampling smoothers `upsample.up_layers.{1,3,5}.weight` keep the reference's own init
 (fill 1/k, :78-79); fc3.weight x WR_FC3_GAIN (peaked class posteriors, so the sampled
 sequence depends on the logits and not only on the noise).
+
+Tacotron (model='tacotron', models/tacotron.py): BatchNorm as above; `decoder.r` = 1 and
+`stop_threshold` = the config's -11 are NOT drawn (the caller sets them); two gains, chosen
+on the CPU with the reference model (tests/golden/make_goldens_tacotron.py asserts the
+conditions and prints the figures):
+  decoder.attn_net.v.weight x TACO_ATTN_GAIN   peaked, moving attention: the generic recipe is
+                               flat (mean peak weight 0.02-0.16; x8 gives 0.06-0.47, x16 hits
+                               a near-tie whose fp64 drift is 8e-4); with x24 the mean peak
+                               weight is TACO_MEASURED['peak'] and the argmax visits
+                               TACO_MEASURED['visited'] positions (T = 70 / 60 steps and
+                               T = 45, r = 2 / 200 steps)
+  decoder.mel_proj.weight x TACO_MEL_GAIN      mean |mel| TACO_MEASURED['mel_abs'] (about 0.2
+                               ungained, which would make a 1e-4 bound say little)
 """
 from __future__ import annotations
 
@@ -40,6 +53,10 @@ FP_DUR_BIAS = 6.0
 FP_DUR_GAIN = 1.5
 FP_MEL_GAIN = 4.0
 WR_FC3_GAIN = 0.25
+TACO_ATTN_GAIN = 24.0
+TACO_MEL_GAIN = 10.0
+# the reference model's figures under those gains (make_goldens_tacotron.py), per case
+TACO_MEASURED = {'peak': (0.627, 0.833), 'visited': (5, 7), 'mel_abs': (5.35, 5.04)}
 
 # forward_tacotron.model and dsp sections of the reference config.yaml (:9-34, :76-106)
 DEFAULT_CONFIG = {
@@ -87,6 +104,14 @@ DEFAULT_CONFIG['vocoder'] = {'model': {
 }, 'generate': {'gen_batched': True, 'target': 11000, 'overlap': 550}}
 
 
+# tacotron.model section of the reference config.yaml (:51-61)
+DEFAULT_CONFIG['tacotron'] = {'model': {
+    'embed_dims': 256, 'encoder_dims': 128, 'decoder_dims': 256, 'postnet_dims': 128,
+    'encoder_k': 16, 'lstm_dims': 512, 'postnet_k': 8, 'num_highways': 4, 'dropout': 0.5,
+    'stop_threshold': -11,
+}}
+
+
 def default_config() -> dict:
     return copy.deepcopy(DEFAULT_CONFIG)
 
@@ -101,8 +126,23 @@ def synthetic_array(key: str, shape, dtype: str, seed: int = 0,
     rng = _rng(seed, key)
     leaf = key.rsplit('.', 1)[-1]
     shape = tuple(shape)
+    if model == 'tacotron':
+        if key == 'decoder.r':
+            return np.ones(shape, dtype=np.int32)
+        if key == 'stop_threshold':
+            return np.full(shape, DEFAULT_CONFIG['tacotron']['model']['stop_threshold'], dtype=np.float32)
     if dtype.startswith('int'):
         return np.zeros(shape, dtype=np.int64)
+    if model == 'tacotron':
+        if '.bnorm.' in key:
+            a = rng.uniform(0.75, 1.25, shape) if leaf in ('weight', 'running_var') else rng.normal(0.0, 0.1, shape)
+            return a.astype(np.float32)
+        a = _generic(rng, key, leaf, shape)
+        if key == 'decoder.attn_net.v.weight':
+            a = a * TACO_ATTN_GAIN
+        elif key == 'decoder.mel_proj.weight':
+            a = a * TACO_MEL_GAIN
+        return a.astype(np.float32)
     if model == 'wavernn':
         if '.up_layers.' in key:
             return np.full(shape, 1.0 / shape[-1], dtype=np.float32)

@@ -84,7 +84,7 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * 18: rejected variants removed — FTMI_BANK_LAST, FTMI_BANK_PAIR, ftmi_conv_args.x_plane /
  * x_fin, ftmi_gru_bidir_fused; ftmi_highway_stack_spread[_ws_bytes|_blocks] added;
  * 19: ftmi_nnls_lbfgsb_*, ftmi_set_resident_cu_limit, the persistent-launch guard,
- * ftmi_griffinlim_iter, ftmi_istft_fused). */
+ * ftmi_griffinlim_iter, ftmi_istft_fused; 20: ftmi_tacotron_decoder[_workspace_bytes]). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -92,7 +92,8 @@ int ftmi_abi_version(void);
 const char *ftmi_build_id(void);
 /* Static string for an error code (FTMI_E_* or hipError_t). */
 const char *ftmi_strerror(int code);
-/* Persistent kernels (ftmi_rnn_bidir, ftmi_highway_stack_spread, ftmi_wavernn) hold every
+/* Persistent kernels (ftmi_rnn_bidir, ftmi_highway_stack_spread, ftmi_wavernn,
+ * ftmi_tacotron_decoder) hold every
  * workgroup of their grid resident while they wait on each other: each checks, before it
  * launches anything, that the kernel's occupancy times the CU count covers its grid, and
  * returns FTMI_E_UNSUPPORTED otherwise (ABI 19).  This sets the CU count the check assumes
@@ -675,6 +676,67 @@ uint32_t ftmi_set_wavernn_spin_limit(uint32_t limit);
 int ftmi_wr_unfold(const float *samples, int32_t B, int32_t L, int32_t target, int32_t overlap,
                    int32_t batched, int32_t mu_law, int32_t n_classes, int32_t wave_len,
                    int32_t fade_len, double *out, ftmi_stream_t stream);
+
+/* ---- Tacotron decoder loop (models/tacotron.py; gen_tacotron.py, train_tacotron.py's
+ * attention pass) ---------------------------------------------------------------------------
+ * Fixed architecture of the reference config (config.yaml:51-61): decoder_dims = 256 (the
+ * context width, 2 encoder_dims), lstm_dims = 512, n_mels = 80, decoder prenet 80 -> 256 ->
+ * 128, LSA with 32 filters of 31 taps, Decoder.max_r = 20.  Anything else, more than
+ * FTMI_TACO_MAX_TOKENS tokens or more than FTMI_TACO_MAX_BATCH items per call returns
+ * FTMI_E_UNSUPPORTED (the host chunks larger batches). */
+enum { FTMI_TACO_MAX_TOKENS = 512, FTMI_TACO_MAX_BATCH = 2, FTMI_TACO_STAMPS = 24 };
+
+/* Arguments of ftmi_tacotron_decoder.  All weights fp32, the reference's tensors unless a
+ * transposition is stated:
+ *   enc, enc_proj (B, T, 256)     encoder output and encoder_proj(encoder output)
+ *   pre_w1t [80][256], pre_w2t [256][128], pre_b1, pre_b2   decoder.prenet fc1 / fc2,
+ *                                 weights TRANSPOSED (free-running mode only)
+ *   gru_wih [768][384], gru_whh [768][256], gru_bih, gru_bhh [768]   decoder.attn_rnn
+ *   lsa_conv [32][2][31], lsa_L [256][32], lsa_Lb [256], lsa_wt [256][256] = attn_net.W.weight
+ *                                 TRANSPOSED, lsa_Wb [256], lsa_v [256]
+ *   rin_w [512][512], rin_b [512] decoder.rnn_input
+ *   l1_*, l2_*                    res_rnn1 / res_rnn2: w_ih, w_hh [2048][512], b_ih, b_hh [2048]
+ *   mel_w [1600][512]             decoder.mel_proj.weight (rows mel * 20 + j, j < r, are read)
+ * Mode: pre_gi == NULL: free-running generate (B = 1) — the kernel feeds the last of each
+ *   step's r frames back through the prenet, applies the reference's stop rule (every value
+ *   of the step's r frames < stop_threshold and t > 10, t = step * r) on the device and writes
+ *   the number of decoder steps taken to *steps_out; the host reads it once after the launch.
+ *   pre_gi (B, n, 768), n = ceil(steps / r): teacher-forced — row (b, s) is
+ *   W_ih[:, 256:] prenet(frame s r - 1 of item b, zero for s = 0) + b_ih, computed before the
+ *   launch; no stop rule, steps_out (optional) receives n.
+ * steps: frames asked for (the reference's `steps` / m.size(2)); n = ceil(steps / r) decoder
+ *   steps at most.  mel_out (B, n r, 80) channels-last frames, attn_out (B, n, T): rows past
+ *   the steps taken are left untouched.
+ * workspace: ftmi_tacotron_decoder_workspace_bytes(B, T) bytes (0: unsupported shape), 16-B
+ *   aligned, zeroed by the call; one per stream. */
+typedef struct ftmi_taco_args {
+  const float *enc, *enc_proj;
+  const float *pre_w1t, *pre_b1, *pre_w2t, *pre_b2;
+  const float *gru_wih, *gru_whh, *gru_bih, *gru_bhh;
+  const float *lsa_conv, *lsa_L, *lsa_Lb, *lsa_wt, *lsa_Wb, *lsa_v;
+  const float *rin_w, *rin_b;
+  const float *l1_wih, *l1_whh, *l1_bih, *l1_bhh;
+  const float *l2_wih, *l2_whh, *l2_bih, *l2_bhh;
+  const float *mel_w;
+  const float *pre_gi;
+  float *mel_out, *attn_out;
+  int32_t *steps_out;
+  uint32_t *status;
+  void *workspace;
+  uint64_t *stamps; /* diagnostic, normally NULL: FTMI_TACO_STAMPS device words that receive
+                       workgroup 0's s_memtime sums per phase (tools/taco_stamps.py) */
+  float stop_threshold;
+  int32_t B, T, r, steps;
+  int32_t decoder_dims, lstm_dims, n_mels, prenet_dims;
+} ftmi_taco_args;
+
+/* The decoder loop of Tacotron.generate (:304-312) / Tacotron.forward (:250-256) as ONE
+ * persistent launch of 256 workgroups (one per CU, checked before the launch: fewer resident
+ * returns FTMI_E_UNSUPPORTED and launches nothing).  Exact fp32 FMA arithmetic.  A workgroup
+ * that cannot meet the others sets FTMI_STATUS_RNN_TIMEOUT in *status: the output is then
+ * invalid.  T in [1, FTMI_TACO_MAX_TOKENS]. */
+int64_t ftmi_tacotron_decoder_workspace_bytes(int32_t B, int32_t T);
+int ftmi_tacotron_decoder(const ftmi_taco_args *args, ftmi_stream_t stream);
 
 #ifdef __cplusplus
 }
