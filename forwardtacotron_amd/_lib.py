@@ -142,6 +142,10 @@ SIGNATURES = {
     'ftmi_wr_unfold': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     'ftmi_tacotron_decoder_workspace_bytes': (c_int64, [c_int, c_int]),
     'ftmi_tacotron_decoder': (c_int, [ctypes.POINTER(TacoArgs), P]),
+    'ftmi_align_workspace_bytes': (c_int64, [c_int, c_int, c_int]),
+    'ftmi_align_dijkstra': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P, P, P]),
+    'ftmi_align_count': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P]),
+    'ftmi_attention_score': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, P, c_int, P, P, P]),
     'ftmi_mel_nnls': (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P,
                               c_float, c_int, P, P]),
     'ftmi_nnls_lbfgsb_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int, c_int]),

@@ -1003,3 +1003,83 @@ def tacotron_decoder(args, device) -> None:
                                 + 80 * args.r * 512 + 2 * args.T * 256)
     launch('ftmi_tacotron_decoder', f'tacotron_decoder[{mode},B={args.B},T={args.T},r={args.r},n={n}]',
            flops, 4.0 * args.B * n * (80 * args.r + args.T), ctypes.byref(args), _stream())
+
+
+# ---- Alignment: durations and attention scores (csrc/align.hip) ------------------------------
+
+_ALIGN_WS = {}  # (device, stream) -> uint8 workspace, grown on demand
+
+
+def align_workspace(B: int, rows: int, T: int, device) -> torch.Tensor:
+    """The direction workspace of ftmi_align_dijkstra, cached per device and stream (it is
+    scratch: nothing in it outlives a launch)."""
+    n = int(_lib.load().ftmi_align_workspace_bytes(B, rows, T))
+    if n == 0:
+        raise _lib.FtmiError(f'the alignment kernels take 1..{TACO_MAX_TOKENS} tokens and at least '
+                             f'one row and item (got B={B}, rows={rows}, T={T}): FTMI_E_UNSUPPORTED')
+    dev = torch.device(device)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), _stream())
+    ws = _ALIGN_WS.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _ALIGN_WS[key] = torch.empty(n, device=device, dtype=torch.uint8)
+    return ws
+
+
+def _align_args(att: torch.Tensor, mel_len: torch.Tensor, x_len: Optional[torch.Tensor]):
+    """(B, rows, T, ld_row, ld_item) of a (B, rows, T) fp32 attention with unit column stride;
+    the length vectors must be int32 [B] on att's device."""
+    _dev(att, mel_len, x_len)
+    if att.dim() != 3 or att.dtype != _f32 or 0 in att.shape:
+        raise ValueError(f'att must be a non-empty (B, rows, T) fp32 tensor, got shape '
+                         f'{tuple(att.shape)} {att.dtype}')
+    B, rows, T = att.shape
+    # a stride of a size-1 dimension is never used
+    ld_row = att.stride(1) if rows > 1 else T
+    ld_item = att.stride(0) if B > 1 else 0
+    if (T > 1 and att.stride(2) != 1) or ld_row < T or ld_item < 0:
+        raise ValueError(f'att needs unit column stride and a row stride >= T, got shape '
+                         f'{tuple(att.shape)} strides {att.stride()}')
+    for name, v in (('mel_len', mel_len), ('x_len', x_len)):
+        if v is not None and (v.dtype != torch.int32 or v.shape != (B,) or not v.is_contiguous()
+                              or v.device != att.device):
+            raise ValueError(f'{name} must be a contiguous int32 [{B}] tensor on {att.device}')
+    return B, rows, T, ld_row, ld_item
+
+
+def align_dijkstra(att: torch.Tensor, mel_len: torch.Tensor, x_len: Optional[torch.Tensor] = None,
+                   want_cost: bool = False, workspace: Optional[torch.Tensor] = None):
+    """Shortest-monotone-path durations (ftmi_align_dijkstra): int32 (B, T) and, with
+    want_cost, the path costs as float64 [B] (else None).  The lengths are NOT checked here
+    (the kernel clamps them); forwardtacotron_amd.align validates them."""
+    B, rows, T, ld_row, ld_item = _align_args(att, mel_len, x_len)
+    ws = align_workspace(B, rows, T, att.device) if workspace is None else workspace
+    dur = torch.empty(B, T, device=att.device, dtype=torch.int32)
+    cost = torch.empty(B, device=att.device, dtype=torch.float64) if want_cost else None
+    launch('ftmi_align_dijkstra', f'align_dijkstra[B={B},rows={rows},T={T}]', 3.0 * B * rows * T,
+           5.0 * B * rows * T, att.data_ptr(), ld_row, ld_item, B, rows, T, mel_len.data_ptr(),
+           _ptr(x_len), dur.data_ptr(), _ptr(cost), ws.data_ptr(), _stream())
+    return dur, cost
+
+
+def align_count(att: torch.Tensor, mel_len: torch.Tensor,
+                x_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention-peak-count durations (ftmi_align_count): int32 (B, T)."""
+    B, rows, T, ld_row, ld_item = _align_args(att, mel_len, x_len)
+    dur = torch.empty(B, T, device=att.device, dtype=torch.int32)
+    launch('ftmi_align_count', f'align_count[B={B},rows={rows},T={T}]', 0, 4.0 * B * rows * T,
+           att.data_ptr(), ld_row, ld_item, B, rows, T, mel_len.data_ptr(), _ptr(x_len),
+           dur.data_ptr(), _stream())
+    return dur
+
+
+def attention_score(att: torch.Tensor, mel_len: torch.Tensor, r: int = 1):
+    """(loc_score, sharp_score), fp32 [B] each (ftmi_attention_score)."""
+    B, rows, T, ld_row, ld_item = _align_args(att, mel_len, None)
+    if r < 1:
+        raise ValueError(f'r must be >= 1, got {r}')
+    loc = torch.empty(B, device=att.device, dtype=_f32)
+    sharp = torch.empty(B, device=att.device, dtype=_f32)
+    launch('ftmi_attention_score', f'attention_score[B={B},rows={rows},T={T}]', 0,
+           4.0 * B * rows * T, att.data_ptr(), ld_row, ld_item, B, rows, T, mel_len.data_ptr(),
+           int(r), loc.data_ptr(), sharp.data_ptr(), _stream())
+    return loc, sharp

@@ -84,7 +84,9 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * 18: rejected variants removed — FTMI_BANK_LAST, FTMI_BANK_PAIR, ftmi_conv_args.x_plane /
  * x_fin, ftmi_gru_bidir_fused; ftmi_highway_stack_spread[_ws_bytes|_blocks] added;
  * 19: ftmi_nnls_lbfgsb_*, ftmi_set_resident_cu_limit, the persistent-launch guard,
- * ftmi_griffinlim_iter, ftmi_istft_fused; 20: ftmi_tacotron_decoder[_workspace_bytes]). */
+ * ftmi_griffinlim_iter, ftmi_istft_fused; 20: ftmi_tacotron_decoder[_workspace_bytes];
+ * added under 20 without a signature change: ftmi_align_workspace_bytes,
+ * ftmi_align_dijkstra, ftmi_align_count, ftmi_attention_score). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -737,6 +739,43 @@ typedef struct ftmi_taco_args {
  * invalid.  T in [1, FTMI_TACO_MAX_TOKENS]. */
 int64_t ftmi_tacotron_decoder_workspace_bytes(int32_t B, int32_t T);
 int ftmi_tacotron_decoder(const ftmi_taco_args *args, ftmi_stream_t stream);
+
+/* ---- Alignment: durations and attention scores from Tacotron's attention (the reference's
+ * utils/duration_extraction.py and utils/metrics.py; train_tacotron.py:129-171) ---------------
+ * att: fp32 (B, rows, T), row stride ld_row >= T, item stride ld_item (floats).  mel_len,
+ * x_len: device int32 [B]; x_len NULL means T.  1 <= T <= FTMI_TACO_MAX_TOKENS (else
+ * FTMI_E_UNSUPPORTED); rows is limited by the workspace only.  One workgroup per item.  The
+ * kernels clamp mel_len to [1, rows] and x_len to [1, T], so no value in those arrays makes
+ * them read or write out of bounds.
+ *
+ * ftmi_align_dijkstra (extract_durations_with_dijkstra): per item, R = mel_len[b], C = x_len[b],
+ *   w[i][j] = (double)(1.0f - att[i][j]) (fp32 subtraction), D[0][0] = 0 (w[0][0] not counted),
+ *   D[i][j] = w[i][j] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]) in fp64 over the predecessors
+ *   that exist: the reference's grid graph (right / down / down-right edges weighted by their
+ *   destination), so D equals scipy's dist_matrix bit for bit.  cost_out[b] (optional double
+ *   [B]) = D[R-1][C-1].  Predecessor ties go to the first of diagonal, up, left.  Backtrack
+ *   from (R-1, C-1); each row's frame is counted for the largest column the path visits in
+ *   that row, so sum(dur_out[b]) == R.  dur_out: int32 (B, T), entries >= C written as 0.
+ *   workspace: ftmi_align_workspace_bytes(B, rows, T) bytes (0: unsupported shape), 16-B
+ *   aligned, one per stream; it need not be zeroed.
+ * ftmi_align_count (extract_durations_per_count): first-index argmax of every row over the
+ *   first C columns, the sequential jump repair (|a[t] - a[t-1]| > 10: a[t] = a[t-1], against
+ *   the repaired predecessor), bincount of the first R entries.
+ * ftmi_attention_score (attention_score): L = mel_len[b] / r, n = min(rows, L);
+ *   first-index argmax over all T columns; loc_out[b] = #{1 <= t < n: |a[t] - a[t-1]| <= r}
+ *   / (L - 1) (NaN for L == 1, like the reference); sharp_out[b] = (sum_{t < n} max_j
+ *   att[t][j]) / rows, summed in fp64 and rounded once.  Either output may be NULL, not both. */
+int64_t ftmi_align_workspace_bytes(int32_t B, int32_t rows, int32_t T);
+int ftmi_align_dijkstra(const float *att, int64_t ld_row, int64_t ld_item, int32_t B, int32_t rows,
+                        int32_t T, const int32_t *mel_len, const int32_t *x_len,
+                        int32_t *dur_out, double *cost_out, void *workspace,
+                        ftmi_stream_t stream);
+int ftmi_align_count(const float *att, int64_t ld_row, int64_t ld_item, int32_t B, int32_t rows,
+                     int32_t T, const int32_t *mel_len, const int32_t *x_len, int32_t *dur_out,
+                     ftmi_stream_t stream);
+int ftmi_attention_score(const float *att, int64_t ld_row, int64_t ld_item, int32_t B,
+                         int32_t rows, int32_t T, const int32_t *mel_len, int32_t r,
+                         float *loc_out, float *sharp_out, ftmi_stream_t stream);
 
 #ifdef __cplusplus
 }
