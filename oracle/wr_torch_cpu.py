@@ -249,10 +249,10 @@ def forward(sd, cfg, x, mels):
     h = torch.cat([x.unsqueeze(-1), m, a1], dim=2)
     h = F.linear(h, sd['I.weight'], sd['I.bias'])
     res = h
-    h1 = _gru_seq(sd, 'rnn1', h, torch.zeros(B, R))
+    h1 = _gru_seq(sd, 'rnn1', h, torch.zeros(B, R, dtype=h.dtype))
     h = h1 + res
     res = h
-    h2 = _gru_seq(sd, 'rnn2', torch.cat([h, a2], dim=2), torch.zeros(B, R))
+    h2 = _gru_seq(sd, 'rnn2', torch.cat([h, a2], dim=2), torch.zeros(B, R, dtype=h.dtype))
     h = h2 + res
     h = F.relu(F.linear(torch.cat([h, a3], dim=2), sd['fc1.weight'], sd['fc1.bias']))
     h = F.relu(F.linear(torch.cat([h, a4], dim=2), sd['fc2.weight'], sd['fc2.bias']))
@@ -307,9 +307,10 @@ def generate(sd, cfg, mels, batched=True, target=11000, overlap=550, mu_law=True
         b_size, seq_len, _ = m.size()
         if steps is not None:
             seq_len = min(seq_len, steps)
-        h1 = torch.zeros(b_size, R)
-        h2 = torch.zeros(b_size, R)
-        x = torch.zeros(b_size, 1)
+        dt = sd['I.weight'].dtype  # the states and the fed-back sample follow the weights
+        h1 = torch.zeros(b_size, R, dtype=dt)
+        h2 = torch.zeros(b_size, R, dtype=dt)
+        x = torch.zeros(b_size, 1, dtype=dt)
         aux_split = [aux[:, :, d * i:d * (i + 1)] for i in range(4)]
         output = []
         for i in range(seq_len):
@@ -327,7 +328,7 @@ def generate(sd, cfg, mels, batched=True, target=11000, overlap=550, mu_law=True
             if trace is not None:
                 trace.append(logits.clone())
             if forced is not None:
-                sample = torch.as_tensor(forced[:, i], dtype=torch.float32)
+                sample = torch.as_tensor(forced[:, i], dtype=dt)
             elif mode == 'MOL':
                 if sampler == 'reference':
                     sample = _ref_mol(logits)

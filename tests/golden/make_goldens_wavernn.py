@@ -21,6 +21,10 @@ Cases (synthetic weights, forwardtacotron_amd/synthetic.py model='wavernn'):
                 (the reference's 20-hop fade-out needs >= 21 frames)
   wr_gen_mol    generate(batched=True, target=400, overlap=40), MOL mode, seed 5
   wr_fold       fold_with_overlap / xfade_and_unfold known answers
+  wr_upsample_taps  (`--taps` only: rewrites no other file) UpsampleNetwork with
+                upsample_factors [2, 3], pad 2, on (2, 80, 7) mels, each smoother
+                up_layers.{1,3}.weight drawn U(0.2, 1.8) / k from PCG64(TAPS_SEED): a trained
+                checkpoint's taps are not uniform, and only non-uniform taps show their order
 """
 from __future__ import annotations
 
@@ -121,5 +125,36 @@ def main():
     np.savez(HERE / 'wr_fold.npz', x=x.numpy(), folded=folded.numpy(), y=y, unfolded=un)
 
 
+TAPS_SEED = 31
+
+
+def draw_taps(rng, scale):
+    """One smoother's (1, 1, 1, k) weight, k = 2 scale + 1: U(0.2, 1.8) / k."""
+    k = 2 * scale + 1
+    return (rng.uniform(0.2, 1.8, (1, 1, 1, k)) / k).astype(np.float32)
+
+
+def taps():
+    torch.set_num_threads(8)
+    ns = reference_classes()
+    cfg = default_config()
+    factors = [2, 3]
+    cfg['vocoder']['model']['upsample_factors'] = factors
+    cfg['dsp']['hop_length'] = int(np.prod(factors))
+    model = ns['WaveRNN'].from_config(cfg)
+    sd = synthetic_state_dict(model, seed=0, model='wavernn')
+    rng = np.random.Generator(np.random.PCG64(TAPS_SEED))
+    mels = (rng.normal(0.0, 1.0, (2, 80, 7)) - 4.0).astype(np.float32)
+    for i, s in enumerate(factors):
+        sd[f'upsample.up_layers.{2 * i + 1}.weight'] = draw_taps(rng, s)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    model.eval()
+    with torch.no_grad():
+        up, aux = model.upsample(torch.from_numpy(mels))
+    np.savez(HERE / 'wr_upsample_taps.npz', mels=mels, w1=sd['upsample.up_layers.1.weight'],
+             w3=sd['upsample.up_layers.3.weight'], up=up.numpy(), aux=aux.numpy())
+    print('wr_upsample_taps', tuple(up.shape), tuple(aux.shape))
+
+
 if __name__ == '__main__':
-    main()
+    taps() if '--taps' in sys.argv[1:] else main()

@@ -25,6 +25,7 @@ from forwardtacotron_amd.wavernn import WaveRNN
 from oracle import wr_torch_cpu as wr
 
 from conftest import load_golden
+from wr_cases import check_draws as _check_draws
 
 pytestmark = pytest.mark.gpu
 
@@ -64,33 +65,6 @@ def test_forward_logits_match_reference():
     err = np.abs(logits - ref)
     assert np.all(err <= 2e-4 + 2e-5 * np.abs(ref)), (err.max(), np.abs(ref).max())
     assert err.mean() < 2e-5
-
-
-def _check_draws(m, cfg, mels, seed, target, overlap, batched=True):
-    smp = m.generate_samples(torch.from_numpy(mels), batched, target, overlap, seed=seed).cpu().numpy()
-    trace = []
-    sd = _sd(m)
-    wr.generate(sd, _cfg(cfg), torch.from_numpy(mels), batched=batched, target=target,
-                overlap=overlap, forced=smp, trace=trace, steps=smp.shape[1])
-    sampler = wr.PhiloxSampler(seed)
-    nc = m.n_classes
-    exact = total = 0
-    for t, logits in enumerate(trace):
-        if m.mode == 'RAW':
-            z = sampler.gumbel_scores(logits, t)
-            idx = np.rint((smp[:, t] + 1.0) * (nc - 1) / 2.0).astype(np.int64)
-            best = z.max(axis=1)
-            got = z[np.arange(z.shape[0]), idx]
-            assert np.all(best - got <= 1e-3), (t, (best - got).max())
-            exact += int(np.sum(np.argmax(z, axis=1) == idx))
-        else:
-            tu, u = sampler.mol_uniforms(t, logits.size(0), nc // 3)
-            x = wr.sample_mol(logits, tu, u).numpy()
-            close = np.abs(x - smp[:, t]) <= 1e-4 + 1e-4 * np.abs(x)
-            exact += int(close.sum())
-        total += logits.size(0)
-    assert exact >= 0.995 * total, (exact, total)
-    return smp
 
 
 def test_generate_raw_draws_match_oracle():

@@ -108,3 +108,18 @@ def test_generate_bounded_steps_is_prefix():
     b = wr.generate(_sd(), _cfg(), torch.from_numpy(g['mels']), target=600, overlap=60,
                     sampler=s, steps=20)
     np.testing.assert_array_equal(a[:, :20], b)
+
+
+def test_upsample_matches_reference_with_trained_like_taps():
+    """Non-uniform smoothers (wr_upsample_taps: factors [2, 3], taps U(0.2, 1.8) / k): the
+    tap order and the layer order show in the output, which uniform 1/k taps hide."""
+    g = np.load(G / 'wr_upsample_taps.npz')
+    sd = _sd()
+    sd['upsample.up_layers.1.weight'] = torch.from_numpy(g['w1'])
+    sd['upsample.up_layers.3.weight'] = torch.from_numpy(g['w3'])
+    assert not np.allclose(g['w1'], g['w1'].flat[0]) and not np.allclose(g['w1'], g['w1'][..., ::-1])
+    cfg = _cfg()
+    cfg['upsample_factors'] = [2, 3]
+    up, aux = wr.upsample(sd, torch.from_numpy(g['mels']), cfg)
+    np.testing.assert_array_equal(up.numpy(), g['up'])
+    np.testing.assert_array_equal(aux.numpy(), g['aux'])
