@@ -146,6 +146,10 @@ SIGNATURES = {
     'ftmi_align_dijkstra': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P, P, P]),
     'ftmi_align_count': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P]),
     'ftmi_attention_score': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, P, c_int, P, P, P]),
+    'ftmi_phoneme_features': (c_int, [P, c_int64, c_int64, c_int, c_int, c_int, P, P, c_int64, c_int,
+                                      P, P, c_int64, c_int, P, c_float, P, P, P, P]),
+    'ftmi_nonzero_moments': (c_int, [P, c_int64, P, P]),
+    'ftmi_normalize_nonzero': (c_int, [P, c_int64, c_float, c_float, P]),
     'ftmi_mel_nnls': (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P,
                               c_float, c_int, P, P]),
     'ftmi_nnls_lbfgsb_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int, c_int]),

@@ -6,6 +6,10 @@
 //                          wavefront, then a backtrack that counts frames per token
 //   align_count_kernel     per-row argmax + sequential jump repair + bincount
 //   attention_score_kernel argmax adjacency and mean peak height
+// and what train_tacotron.py:23-104 makes of the durations (extract_pitch_energy):
+//   phoneme_features_kernel   per-token means of the frame energy and of the voiced pitch
+//   nonzero_moments_kernel    count / mean / population std of the non-zero phoneme pitches
+//   normalize_nonzero_kernel  (v - mean) / std on them, in place
 // One workgroup per item; no workgroup waits on another; every loop bound is known at launch.
 #include "common.h"
 
@@ -277,6 +281,162 @@ int al_check(const float *att, int64_t ld_row, int64_t ld_item, int32_t B, int32
   return FTMI_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Phoneme-level pitch and energy (train_tacotron.py:37-104).  Frames pass through LDS in chunks
+// of PF_CHUNK: a thread per frame computes energy[t] = sqrt(sum_k exp(mel[k][t])^2) in fp64 (for
+// a fixed bin the loads of a wave are contiguous along t) and stages the frame's pitch, then a
+// thread per token adds the chunk's part of its frame range [cum[i], cum[i+1]) to its running
+// fp64 sums, in t order.  Nothing here depends on B or on which chunk a frame falls in, so an
+// item's result is the same bits in every batch.
+constexpr int PF_NT = 1024;    // >= 2 * AL_TMAX: a thread per token, two frames per thread and chunk
+constexpr int PF_NW = PF_NT / 64;
+constexpr int PF_CHUNK = 2048;  // frames per LDS pass: 8 B energy + 4 B pitch each
+constexpr int PF_KU = 8;        // mel loads in flight per thread
+
+__global__ __launch_bounds__(PF_NT) void phoneme_features_kernel(
+    const float *__restrict__ mel, int64_t ld_bin, int64_t ld_item, int n_mels, int rows,
+    const int32_t *__restrict__ mel_len, const int32_t *__restrict__ dur, int64_t ld_dur, int T,
+    const int32_t *__restrict__ x_len, const float *__restrict__ pitch, int64_t ld_pitch, int P,
+    const int32_t *__restrict__ pitch_len, float pitch_max_freq, float *__restrict__ pitch_out,
+    float *__restrict__ energy_out, int32_t *__restrict__ dur_sum) {
+  __shared__ double s_e[PF_CHUNK];
+  __shared__ float s_p[PF_CHUNK];
+  __shared__ long long s_w[2][PF_NW];  // per wave: sum of the clamped durations, of the raw ones
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int L = al_clamp(mel_len[b], 0, rows);
+  const int C = al_clamp(x_len ? x_len[b] : T, 0, T);
+  const int PL = pitch ? al_clamp(pitch_len[b], 0, P) : 0;
+  const int ntok = min(C, L);  // the reference's loop zips over range(mel_len)
+
+  // cum[i], cum[i + 1] of token i = tid: a block scan of max(dur, 0) over the first C columns
+  // (int64: no duration array overflows it); the raw sum is what the host compares with mel_len
+  const int d = dur[(int64_t)b * ld_dur + min(tid, T - 1)];
+  long long dc = tid < C ? max(d, 0) : 0, dr = tid < C ? d : 0;
+  const long long own = dc;
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long uc = __shfl_up(dc, o, 64), ur = __shfl_up(dr, o, 64);
+    if (lane >= o) { dc += uc; dr += ur; }
+  }
+  if (lane == 63) { s_w[0][wave] = dc; s_w[1][wave] = dr; }
+  __syncthreads();
+  long long raw = 0;
+  for (int w = 0; w < PF_NW; ++w) {
+    if (w < wave) dc += s_w[0][w];
+    raw += s_w[1][w];
+  }
+  if (tid == 0) dur_sum[b] = (int32_t)(raw > 0x7fffffffLL ? 0x7fffffffLL : (raw < -0x80000000LL ? -0x80000000LL : raw));
+  const int fb = (int)(dc < L ? dc : L);                // frame range [fa, fb), clamped to mel_len
+  const int fa = (int)(dc - own < L ? dc - own : L);
+
+  const float *m = mel + (int64_t)b * ld_item;
+  const float *pb = pitch ? pitch + (int64_t)b * ld_pitch : nullptr;
+  double es = 0.0, ps = 0.0;
+  int pc = 0;
+  for (int c0 = 0; c0 < L; c0 += PF_CHUNK) {
+    const int n = min(PF_CHUNK, L - c0);
+    for (int f = tid; f < n; f += PF_NT) {
+      const int t = c0 + f;  // < L <= rows
+      double s = 0.0;
+      for (int k0 = 0; k0 < n_mels; k0 += PF_KU) {
+        float v[PF_KU];  // no branch around a load: the bin index is clamped, the sum is masked
+#pragma unroll
+        for (int u = 0; u < PF_KU; ++u) v[u] = m[(int64_t)min(k0 + u, n_mels - 1) * ld_bin + t];
+#pragma unroll
+        for (int u = 0; u < PF_KU; ++u) {
+          const double e = exp((double)v[u]);
+          s = k0 + u < n_mels ? __dadd_rn(s, __dmul_rn(e, e)) : s;
+        }
+      }
+      s_e[f] = sqrt(s);
+      if (pb) {
+        const float pv = pb[min(t, max(PL - 1, 0))];
+        s_p[f] = t < PL ? pv : 0.0f;  // 0: never kept
+      }
+    }
+    __syncthreads();
+    if (tid < ntok) {
+      const int lo = max(fa, c0) - c0, hi = min(fb, c0 + n) - c0;
+      for (int f = lo; f < hi; ++f) {
+        es += s_e[f];
+        if (pb) {
+          const float pv = s_p[f];
+          if (pv != 0.0f && pv < pitch_max_freq) { ps += (double)pv; pc += 1; }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < T) {
+    const bool live = tid < ntok;
+    energy_out[(int64_t)b * T + tid] = live && fb > fa ? (float)(es / (double)(fb - fa)) : 0.0f;
+    if (pb) pitch_out[(int64_t)b * T + tid] = live && pc > 0 ? (float)(ps / (double)pc) : 0.0f;
+  }
+}
+
+// Count, mean and population standard deviation of the non-zero entries of v[0 .. n), fp64, two
+// passes (sum (v - mean)^2, like np.std).  One workgroup: thread i adds entries i, i + MO_NT, ...
+// in that order, and the MO_NT partials meet in a fixed tree, so the result repeats bit for bit.
+constexpr int MO_NT = 1024;
+constexpr int MO_U = 8;  // loads in flight per thread
+
+__device__ __forceinline__ double mo_block_sum(double v, double *s, int tid) {
+  __syncthreads();  // s may still be read from the previous sum
+  s[tid] = v;
+  __syncthreads();
+  for (int o = MO_NT / 2; o > 0; o >>= 1) {
+    if (tid < o) s[tid] += s[tid + o];
+    __syncthreads();
+  }
+  return s[0];
+}
+
+__global__ __launch_bounds__(MO_NT) void nonzero_moments_kernel(const float *__restrict__ v,
+                                                                int64_t n, double *__restrict__ out) {
+  __shared__ double s_red[MO_NT];
+  const int tid = threadIdx.x;
+  double cnt = 0.0, sum = 0.0;  // a count below 2^53 is exact in fp64
+  for (int64_t i0 = tid; i0 < n; i0 += (int64_t)MO_NT * MO_U) {
+    float x[MO_U];
+#pragma unroll
+    for (int u = 0; u < MO_U; ++u) x[u] = v[min(i0 + (int64_t)u * MO_NT, n - 1)];
+#pragma unroll
+    for (int u = 0; u < MO_U; ++u)
+      if (i0 + (int64_t)u * MO_NT < n && x[u] != 0.0f) { cnt += 1.0; sum += (double)x[u]; }
+  }
+  cnt = mo_block_sum(cnt, s_red, tid);
+  sum = mo_block_sum(sum, s_red, tid);
+  const double mean = cnt > 0.0 ? sum / cnt : 0.0;
+  double sq = 0.0;
+  for (int64_t i0 = tid; i0 < n; i0 += (int64_t)MO_NT * MO_U) {
+    float x[MO_U];
+#pragma unroll
+    for (int u = 0; u < MO_U; ++u) x[u] = v[min(i0 + (int64_t)u * MO_NT, n - 1)];
+#pragma unroll
+    for (int u = 0; u < MO_U; ++u)
+      if (i0 + (int64_t)u * MO_NT < n && x[u] != 0.0f) {
+        const double dv = (double)x[u] - mean;
+        sq = __dadd_rn(sq, __dmul_rn(dv, dv));
+      }
+  }
+  sq = mo_block_sum(sq, s_red, tid);
+  if (tid == 0) {
+    out[0] = cnt;
+    out[1] = mean;
+    out[2] = cnt > 0.0 ? sqrt(sq / cnt) : 0.0;
+  }
+}
+
+// v = (v - mean) / std where v != 0: an fp32 subtraction, then the correctly rounded fp32
+// quotient, which is what numpy's `v -= mean; v /= std` computes.
+__global__ __launch_bounds__(256) void normalize_nonzero_kernel(float *__restrict__ v, int64_t n,
+                                                                float mean, float std) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
+    const float x = v[i];
+    if (x != 0.0f) v[i] = __fdiv_rn(__fsub_rn(x, mean), std);
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t ftmi_align_workspace_bytes(int32_t B, int32_t rows, int32_t T) {
@@ -324,6 +484,50 @@ extern "C" int ftmi_attention_score(const float *att, int64_t ld_row, int64_t ld
   if (((uintptr_t)loc_out & 3u) || ((uintptr_t)sharp_out & 3u)) return FTMI_E_ALIGN;
   hipLaunchKernelGGL(attention_score_kernel, dim3(B), dim3(AL_NT), 0, ftmi_hs(stream), att, ld_row,
                      ld_item, rows, T, mel_len, r, loc_out, sharp_out);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_phoneme_features(const float *mel, int64_t ld_bin, int64_t ld_item, int32_t B,
+                                     int32_t n_mels, int32_t rows, const int32_t *mel_len,
+                                     const int32_t *dur, int64_t ld_dur, int32_t T,
+                                     const int32_t *x_len, const float *pitch, int64_t ld_pitch,
+                                     int32_t P, const int32_t *pitch_len, float pitch_max_freq,
+                                     float *pitch_out, float *energy_out, int32_t *dur_sum,
+                                     ftmi_stream_t stream) {
+  if (!mel || !mel_len || !dur || !energy_out || !dur_sum) return FTMI_E_ARG;
+  if (B <= 0 || n_mels <= 0 || rows <= 0 || T <= 0) return FTMI_E_ARG;
+  if ((pitch != nullptr) != (pitch_len != nullptr) || (pitch != nullptr) != (pitch_out != nullptr))
+    return FTMI_E_ARG;  // pitch, its lengths and its output come together or not at all
+  if (pitch && P <= 0) return FTMI_E_ARG;
+  if (T > AL_TMAX) return FTMI_E_UNSUPPORTED;
+  if (ld_bin < rows || ld_item < 0 || ld_dur < T || (pitch && ld_pitch < P)) return FTMI_E_SHAPE;
+  if (((uintptr_t)mel | (uintptr_t)mel_len | (uintptr_t)dur | (uintptr_t)x_len | (uintptr_t)pitch |
+       (uintptr_t)pitch_len | (uintptr_t)pitch_out | (uintptr_t)energy_out | (uintptr_t)dur_sum) & 3u)
+    return FTMI_E_ALIGN;
+  hipLaunchKernelGGL(phoneme_features_kernel, dim3(B), dim3(PF_NT), 0, ftmi_hs(stream), mel, ld_bin,
+                     ld_item, n_mels, rows, mel_len, dur, ld_dur, T, x_len, pitch, ld_pitch, P,
+                     pitch_len, pitch_max_freq, pitch_out, energy_out, dur_sum);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_nonzero_moments(const float *values, int64_t n, double *out,
+                                    ftmi_stream_t stream) {
+  if (!values || !out || n <= 0) return FTMI_E_ARG;
+  if (((uintptr_t)values & 3u) || ((uintptr_t)out & 7u)) return FTMI_E_ALIGN;
+  hipLaunchKernelGGL(nonzero_moments_kernel, dim3(1), dim3(MO_NT), 0, ftmi_hs(stream), values, n, out);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_normalize_nonzero(float *values, int64_t n, float mean, float std,
+                                      ftmi_stream_t stream) {
+  if (!values || n <= 0) return FTMI_E_ARG;
+  if ((uintptr_t)values & 3u) return FTMI_E_ALIGN;
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(normalize_nonzero_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)),
+                     dim3(256), 0, ftmi_hs(stream), values, n, mean, std);
   FTMI_CHECK_LAUNCH();
   return FTMI_OK;
 }

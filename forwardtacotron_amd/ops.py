@@ -1083,3 +1083,84 @@ def attention_score(att: torch.Tensor, mel_len: torch.Tensor, r: int = 1):
            4.0 * B * rows * T, att.data_ptr(), ld_row, ld_item, B, rows, T, mel_len.data_ptr(),
            int(r), loc.data_ptr(), sharp.data_ptr(), _stream())
     return loc, sharp
+
+
+# ---- Phoneme-level pitch and energy (csrc/align.hip) -----------------------------------------
+
+def phoneme_features(mel: torch.Tensor, mel_len: torch.Tensor, dur: torch.Tensor,
+                     x_len: Optional[torch.Tensor] = None, pitch: Optional[torch.Tensor] = None,
+                     pitch_len: Optional[torch.Tensor] = None, pitch_max_freq: float = 600.0):
+    """Per-token means of the frame energy and of the voiced frame pitch
+    (ftmi_phoneme_features): mel (B, n_mels, rows) fp32 with unit frame stride, dur (B, T) int32,
+    pitch (B, P) fp32 with pitch_len, or both None -> (pitch_char or None, energy_char, dur_sum):
+    fp32 (B, T), fp32 (B, T), int32 [B].  The lengths are NOT checked here (the kernel clamps
+    them); forwardtacotron_amd.align validates them and compares dur_sum with mel_len."""
+    _dev(mel, mel_len, dur, x_len, pitch, pitch_len)
+    if mel.dim() != 3 or mel.dtype != _f32 or 0 in mel.shape:
+        raise ValueError(f'mel must be a non-empty (B, n_mels, rows) fp32 tensor, got shape '
+                         f'{tuple(mel.shape)} {mel.dtype}')
+    B, n_mels, rows = mel.shape
+    if dur.dim() != 2 or dur.dtype != torch.int32 or dur.size(0) != B or dur.size(1) == 0:
+        raise ValueError(f'dur must be a ({B}, T) int32 tensor, got shape {tuple(dur.shape)} {dur.dtype}')
+    T = dur.size(1)
+    # a stride of a size-1 dimension is never used
+    ld_bin = mel.stride(1) if n_mels > 1 else rows
+    ld_item = mel.stride(0) if B > 1 else 0
+    ld_dur = dur.stride(0) if B > 1 else T
+    if (rows > 1 and mel.stride(2) != 1) or ld_bin < rows or ld_item < 0:
+        raise ValueError(f'mel needs unit frame stride and a bin stride >= rows, got shape '
+                         f'{tuple(mel.shape)} strides {mel.stride()}')
+    if (T > 1 and dur.stride(1) != 1) or ld_dur < T:
+        raise ValueError(f'dur needs unit column stride and a row stride >= T, got strides {dur.stride()}')
+    if (pitch is None) != (pitch_len is None):
+        raise ValueError('pitch and pitch_len come together')
+    P = ld_pitch = 0
+    if pitch is not None:
+        if pitch.dim() != 2 or pitch.dtype != _f32 or pitch.size(0) != B or pitch.size(1) == 0:
+            raise ValueError(f'pitch must be a ({B}, P) fp32 tensor, got shape {tuple(pitch.shape)} '
+                             f'{pitch.dtype}')
+        P = pitch.size(1)
+        ld_pitch = pitch.stride(0) if B > 1 else P
+        if (P > 1 and pitch.stride(1) != 1) or ld_pitch < P:
+            raise ValueError(f'pitch needs unit column stride and a row stride >= P, got strides '
+                             f'{pitch.stride()}')
+    for name, v in (('mel_len', mel_len), ('x_len', x_len), ('pitch_len', pitch_len)):
+        if v is not None and (v.dtype != torch.int32 or v.shape != (B,) or not v.is_contiguous()
+                              or v.device != mel.device):
+            raise ValueError(f'{name} must be a contiguous int32 [{B}] tensor on {mel.device}')
+    energy_out = torch.empty(B, T, device=mel.device, dtype=_f32)
+    pitch_out = None if pitch is None else torch.empty(B, T, device=mel.device, dtype=_f32)
+    dur_sum = torch.empty(B, device=mel.device, dtype=torch.int32)
+    launch('ftmi_phoneme_features', f'phoneme_features[B={B},rows={rows},T={T}]',
+           30.0 * B * n_mels * rows, 4.0 * B * (n_mels + 1) * rows, mel.data_ptr(), ld_bin, ld_item,
+           B, n_mels, rows, mel_len.data_ptr(), dur.data_ptr(), ld_dur, T, _ptr(x_len), _ptr(pitch),
+           ld_pitch, P, _ptr(pitch_len), float(pitch_max_freq), _ptr(pitch_out),
+           energy_out.data_ptr(), dur_sum.data_ptr(), _stream())
+    return pitch_out, energy_out, dur_sum
+
+
+def _flat_f32(values: torch.Tensor) -> int:
+    _dev(values)
+    if values.dtype != _f32 or not values.is_contiguous() or values.numel() == 0:
+        raise ValueError(f'values must be a non-empty contiguous fp32 tensor, got shape '
+                         f'{tuple(values.shape)} {values.dtype}')
+    return values.numel()
+
+
+def nonzero_moments(values: torch.Tensor) -> torch.Tensor:
+    """float64 [3] on the device: the count of non-zero entries of `values`, their mean and
+    their population standard deviation (ftmi_nonzero_moments); 0, 0, 0 without any."""
+    n = _flat_f32(values)
+    out = torch.empty(3, device=values.device, dtype=torch.float64)
+    launch('ftmi_nonzero_moments', f'nonzero_moments[n={n}]', 4.0 * n, 8.0 * n,
+           values.data_ptr(), n, out.data_ptr(), _stream())
+    return out
+
+
+def normalize_nonzero(values: torch.Tensor, mean: float, std: float) -> torch.Tensor:
+    """values = (values - mean) / std in place where values != 0, in fp32
+    (ftmi_normalize_nonzero).  Returns values."""
+    n = _flat_f32(values)
+    launch('ftmi_normalize_nonzero', f'normalize_nonzero[n={n}]', 2.0 * n, 8.0 * n,
+           values.data_ptr(), n, float(mean), float(std), _stream())
+    return values

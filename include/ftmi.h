@@ -86,7 +86,8 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * 19: ftmi_nnls_lbfgsb_*, ftmi_set_resident_cu_limit, the persistent-launch guard,
  * ftmi_griffinlim_iter, ftmi_istft_fused; 20: ftmi_tacotron_decoder[_workspace_bytes];
  * added under 20 without a signature change: ftmi_align_workspace_bytes,
- * ftmi_align_dijkstra, ftmi_align_count, ftmi_attention_score). */
+ * ftmi_align_dijkstra, ftmi_align_count, ftmi_attention_score; ftmi_phoneme_features,
+ * ftmi_nonzero_moments, ftmi_normalize_nonzero). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -776,6 +777,43 @@ int ftmi_align_count(const float *att, int64_t ld_row, int64_t ld_item, int32_t 
 int ftmi_attention_score(const float *att, int64_t ld_row, int64_t ld_item, int32_t B,
                          int32_t rows, int32_t T, const int32_t *mel_len, int32_t r,
                          float *loc_out, float *sharp_out, ftmi_stream_t stream);
+
+/* ---- Phoneme-level pitch and energy from the durations (the reference's extract_pitch_energy
+ * and normalize_values, train_tacotron.py:23-104) ------------------------------------------------
+ * ftmi_phoneme_features: one launch over the batch, one workgroup per item, no workspace.
+ *   mel: fp32 log-mel (B, n_mels, rows), unit frame stride, bin stride ld_bin >= rows, item
+ *   stride ld_item (floats).  dur: int32 (B, T), row stride ld_dur >= T, 1 <= T <=
+ *   FTMI_TACO_MAX_TOKENS (else FTMI_E_UNSUPPORTED).  mel_len, x_len (NULL: T): device int32 [B].
+ *   pitch: fp32 (B, P) raw frame pitch, row stride ld_pitch >= P, with pitch_len int32 [B];
+ *   pitch, pitch_len and pitch_out are given together or all NULL (energy only).
+ *   Per item, L = mel_len[b], C = x_len[b], PL = pitch_len[b], clamped into [0, rows], [0, T],
+ *   [0, P]; cum = running sum of max(dur[i], 0) over i < C; token i covers frames
+ *   [min(cum[i], L), min(cum[i+1], L)).
+ *     energy[t]     = sqrt(sum_k e_k * e_k), e_k = exp((double)mel[k][t]), fp64, k ascending
+ *     energy_out[i] = (float)(sum of energy[t] over the token's frames, t ascending, fp64 /
+ *                     their count); 0 for an empty range
+ *     pitch_out[i]  = the same mean over the frames t < PL whose pitch v has v != 0.0f and
+ *                     v < pitch_max_freq (both tests in fp32); 0 if none is left
+ *   Tokens i >= min(C, L) get 0 in both outputs (the reference's loop visits range(mel_len)
+ *   tokens only).  Frames >= L, duration columns >= C and pitch entries >= PL reach no result.
+ *   dur_sum[b] = sum of dur[b][i], i < C, negative entries included, saturated to int32: the
+ *   caller compares it with mel_len (the reference's assert); it is not a device status word.
+ *   pitch_out, energy_out: fp32 (B, T) contiguous.  The order of every sum is fixed: an item's
+ *   result does not depend on B.  Domain: finite mel values <= 40.
+ * ftmi_nonzero_moments: out[0 .. 3) (device double) = the count of entries v != 0 of values[0 .. n),
+ *   their mean, and their population standard deviation sqrt(sum (v - mean)^2 / count), in fp64
+ *   with a fixed order of additions (1024 partials, a fixed tree): the same bits on every call.
+ *   No non-zero entry: 0, 0, 0.
+ * ftmi_normalize_nonzero: values[i] = (values[i] - mean) / std in place where values[i] != 0: an
+ *   fp32 subtraction, then the correctly rounded fp32 quotient. */
+int ftmi_phoneme_features(const float *mel, int64_t ld_bin, int64_t ld_item, int32_t B,
+                          int32_t n_mels, int32_t rows, const int32_t *mel_len, const int32_t *dur,
+                          int64_t ld_dur, int32_t T, const int32_t *x_len, const float *pitch,
+                          int64_t ld_pitch, int32_t P, const int32_t *pitch_len,
+                          float pitch_max_freq, float *pitch_out, float *energy_out,
+                          int32_t *dur_sum, ftmi_stream_t stream);
+int ftmi_nonzero_moments(const float *values, int64_t n, double *out, ftmi_stream_t stream);
+int ftmi_normalize_nonzero(float *values, int64_t n, float mean, float std, ftmi_stream_t stream);
 
 #ifdef __cplusplus
 }
