@@ -81,6 +81,8 @@ SIGNATURES = {
     'ftmi_conv_bank_halves_ws_floats': (c_int64, [c_int, c_int, c_int, c_int]),
     'ftmi_conv_bank_halves_image_bytes': (c_int64, [c_int, c_int, c_int]),
     'ftmi_conv_bank_halves_image': (c_int, [P, c_int, c_int, c_int, P, P]),
+    'ftmi_embed_bank': (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_int64,
+                                c_int, P, P]),
     'ftmi_highway': (c_int, [P, c_int64, c_int64, c_int, P, P, P, P, P, c_int64, c_int, P, P]),
     'ftmi_highway_split': (c_int, [P, c_int64, c_int64, c_int, P, P, P, P, P, c_int64, c_int, P,
                                    c_int, P, P]),

@@ -306,6 +306,48 @@ class CBHG(Packed):
         bank = ops.conv_bank(ops.split_rows(x) if xin else x, bank_w, self.K, self.channels,
                              scale, shift, w_split=bank3, pool=pooled, split_out=split,
                              x_split=xin, w_image=img)
+        return self._after_bank(bank, x, pooled, split)
+
+    def embed_bank_table(self, embedding_weight: torch.Tensor) -> torch.Tensor:
+        """The conv bank folded through an embedding (ops.embed_bank_table: [S][K(K+1)/2]
+        [channels] fp32, built in fp64), cached like every pack: keyed on this module's
+        parameters and the embedding weight's identity / version / device, so it is rebuilt
+        after load_state_dict, .to or an in-place change of either."""
+        key = (self._pack_key(), embedding_weight.data_ptr(), embedding_weight._version,
+               embedding_weight.device)
+        cache = self.__dict__.get('_ftmi_embed_table')
+        if cache is None or cache[0] != key:
+            with torch.no_grad():
+                cache = (key, ops.embed_bank_table(
+                    embedding_weight, [c.conv.weight for c in self.conv1d_bank]))
+            self.__dict__['_ftmi_embed_table'] = cache
+        return cache[1]
+
+    def forward_ids(self, x_ids: torch.Tensor, embedding_weight: torch.Tensor) -> torch.Tensor:
+        """forward_cl(embedding(x_ids)): (B, T) ids -> (B, T, 2*channels).  From
+        ops.EMBED_BANK_MIN_ROWS rows on the conv bank is a gather of `embed_bank_table` rows
+        (ops.embed_bank) instead of a GEMM over the embedded rows, which then only serve as
+        the proj2 residual."""
+        w = embedding_weight.detach()
+        h = ops.embedding(x_ids, w)
+        # shapes without a table kernel (ops.embed_bank_ok) keep the GEMM bank, like few rows
+        if (x_ids.numel() < ops.EMBED_BANK_MIN_ROWS
+                or w.size(1) != self.conv1d_bank[0].conv.in_channels
+                or not ops.embed_bank_ok(w.size(0), 1, self.K, self.channels)):
+            return self.forward_cl(h)
+        _, scale, shift, _, bank3 = self.packed_weights()[:5]
+        # split rows exactly where forward_cl's pooled bank would store them (proj1 then reads
+        # them on the f16x3 slab kernel); fp32 rows elsewhere and under ops.exact_paths()
+        split = ops.SPLIT_ROWS and ops.bank_pools(h, self.K, self.channels, w_split=bank3)
+        bank = ops.embed_bank(x_ids, self.embed_bank_table(w), 1, self.K, self.channels, scale,
+                              shift, pool=True, split_out=split)
+        return self._after_bank(bank, h, True, split)
+
+    def _after_bank(self, bank: torch.Tensor, x: torch.Tensor, pooled: bool,
+                    split: bool) -> torch.Tensor:
+        """proj1 -> proj2 + residual x -> highways -> GRU on the bank output (pooled: the
+        maxpool already applied; split: stored as f16x3 split rows)."""
+        bank_w, scale, shift, w_pre, bank3, pre3, img = self.packed_weights()
         y = self.conv_project1.forward_cl(bank, maxpool=not pooled, x_split=split)
         del bank
         y = self.conv_project2.forward_cl(y, residual=x)

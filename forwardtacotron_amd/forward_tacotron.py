@@ -351,7 +351,8 @@ class ForwardTacotron(nn.Module):
         the caller); enc, the offsets and the LSTM input projection are consumed by this
         call's decoder — the next replay waits for the decoder's completion event
         (generate() records it), so calls on different streams never overwrite buffers a
-        decoder still reads.  The entry keeps every module's weight pack alive and the
+        decoder still reads.  The entry keeps every module's weight packs (the fused-stack blocks and the
+        table-gather bank's table too) alive and the
         model-wide weights key of its capture: after each replay (while it runs) the key is
         compared with the model's, and on a change (load_state_dict, .to(), in-place
         updates) every captured phase is dropped and the call falls back to the eager phase
@@ -388,7 +389,8 @@ class ForwardTacotron(nn.Module):
                 torch.cuda.synchronize(x.device)
                 seen[key] = -1
                 return None
-            packs = [m.__dict__.get('_ftmi_pack') for m in self.modules()]
+            packs = [m.__dict__.get(k) for m in self.modules()
+                     for k in ('_ftmi_pack', '_ftmi_stack', '_ftmi_embed_table')]
             ent = {'g': g, 'sx': sx, 'outs': outs, 'wkey': wkey, 'packs': packs,
                    'done': torch.cuda.Event()}
             ent['done'].record(torch.cuda.current_stream(x.device))
@@ -441,7 +443,7 @@ class ForwardTacotron(nn.Module):
         for s in (s_pitch, s_energy, s_prenet):
             s.wait_stream(main)
         with torch.cuda.stream(s_prenet):
-            enc = self.prenet.forward_cl(ops.embedding(x, self.embedding.weight.detach()))
+            enc = self.prenet.forward_ids(x, self.embedding.weight)
             # the LSTM input projection right after the prenet; the pitch / energy terms are
             # added to its rows once the predictors are done (_folded_series_weights)
             xp = self.lstm.project(enc)
@@ -565,7 +567,7 @@ class ForwardTacotron(nn.Module):
         dur_hat has already been clipped / filled in place); xp: the LSTM input projection
         with the pitch / energy terms if already queued (then enc is not read)."""
         if enc is None:
-            enc = self.prenet.forward_cl(ops.embedding(x, self.embedding.weight.detach()))
+            enc = self.prenet.forward_ids(x, self.embedding.weight)
         if xp is None:
             wp, bp, we, be = self._series_proj_weights()
             ops.series_proj_add(enc, pitch_hat, wp, bp, self.pitch_strength, energy_hat, we, be,

@@ -498,6 +498,71 @@ def split_rows(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+# A conv bank whose input is an embedding runs as a table gather (embed_bank) from this many
+# (b, t) rows on; below it the GEMM bank (conv_bank) takes the embedded rows.  Interleaved
+# A/B (tools/ab_bench.py, DESIGN.md §4 `embed_bank_kernel`): c3 (12,800 rows) 7.85-7.94 ->
+# 7.56-7.77 ms/step; c2 (120 rows) 2.60-2.68 with the table bank against 2.59-2.62 without —
+# inside the spread, so the few-row GEMM bank stays.
+EMBED_BANK_MIN_ROWS = 256
+EMBED_BANK_TILE = (16, 64)  # embed_bank.hip EB_ROWS, EB_ROWS * EB_WAVES: rows per wave / workgroup
+EMBED_BANK_KMAX, EMBED_BANK_PANEL = 16, 256  # embed_bank.hip EB_KMAX, EB_PANEL
+
+
+def embed_bank_taps(kmin: int, kmax: int) -> int:
+    """Rows per symbol of an embed_bank table: one per (kernel size, tap)."""
+    return (kmax * (kmax + 1) - kmin * (kmin - 1)) // 2
+
+
+def embed_bank_table(emb: torch.Tensor, conv_weights) -> torch.Tensor:
+    """The table of `embed_bank` for an embedding weight (S, Cin) and nn.Conv1d weights
+    (Cout, Cin, k) of consecutive kernel sizes: [S][taps][Cout] fp32 with
+    Tab[s][(k, j)] = W_k[:, :, j] . E[s], taps ordered (k ascending, j = 0..k-1) — computed
+    in fp64 and rounded once.  Pack-time work (a torch einsum), once per weights version."""
+    _dev(emb, *conv_weights)
+    e = emb.detach().double()
+    parts = [torch.einsum('ncj,sc->sjn', w.detach().double(), e) for w in conv_weights]
+    return torch.cat(parts, 1).float().contiguous()
+
+
+def embed_bank_ok(num_rows: int, kmin: int, kmax: int, Cout: int) -> bool:
+    """Whether ftmi_embed_bank has a kernel for the shape (embed_bank.hip: kernel sizes up to
+    16, Cout a multiple of 256, a table below 2 GiB); elsewhere it returns
+    FTMI_E_UNSUPPORTED and the caller keeps the GEMM bank."""
+    return (1 <= kmin <= kmax <= EMBED_BANK_KMAX and Cout > 0 and Cout % EMBED_BANK_PANEL == 0
+            and num_rows * embed_bank_taps(kmin, kmax) * Cout * 4 < 1 << 31)
+
+
+def embed_bank(ids: torch.Tensor, table: torch.Tensor, kmin: int, kmax: int, Cout: int,
+               scale: torch.Tensor, shift: torch.Tensor, pool: bool = False,
+               split_out: bool = False) -> torch.Tensor:
+    """Conv bank (kernel sizes kmin..kmax, pad k//2, ReLU then folded BN) of the embedded ids
+    as a gather of `embed_bank_table` rows summed in tap order: (B, T) int64 ->
+    (B, T, G*Cout), G = kmax - kmin + 1.  pool: the CBHG maxpool(2, 1) of it; split_out: stored
+    as f16x3 split rows (range-checked into the status word).  An id outside the table
+    contributes zero rows, like `embedding`'s zero row."""
+    _dev(ids, table, scale, shift)
+    ids = ids.contiguous()
+    if ids.dtype != torch.int64:
+        ids = ids.long()
+    B, T = ids.shape
+    G, taps = kmax - kmin + 1, embed_bank_taps(kmin, kmax)
+    if table.dim() != 3 or table.size(1) != taps or table.size(2) != Cout or table.dtype != _f32 \
+            or not table.is_contiguous():
+        raise ValueError(f'embed_bank: table {tuple(table.shape)} is not contiguous fp32 '
+                         f'[S][{taps}][{Cout}]')
+    if scale.numel() != G * Cout or shift.numel() != G * Cout:
+        raise ValueError('embed_bank: scale / shift must hold G*Cout values')
+    y = torch.empty(B, T, G * Cout, device=table.device, dtype=_f32)
+    M = B * T
+    launch('ftmi_embed_bank', f'embed_bank[M={M},{f"K={kmax}" if kmin == 1 else f"k={kmin}-{kmax}"},'
+           f'Cout={Cout}{",pool" if pool else ""}{",split" if split_out else ""}]',
+           1.0 * M * taps * Cout, 4.0 * M * taps * Cout + 8.0 * M + 4.0 * M * G * Cout,
+           ids.data_ptr(), B, T, table.data_ptr(), table.size(0), kmin, kmax, Cout,
+           scale.data_ptr(), shift.data_ptr(), y.data_ptr(), y.stride(-2),
+           int(pool) | (2 * int(split_out)), status_word(table.device).data_ptr(), _stream())
+    return y
+
+
 def highway(x: torch.Tensor, w12: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor,
             out: Optional[torch.Tensor] = None, mma: Optional[int] = None,
             w_split: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -87,7 +87,7 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * ftmi_griffinlim_iter, ftmi_istft_fused; 20: ftmi_tacotron_decoder[_workspace_bytes];
  * added under 20 without a signature change: ftmi_align_workspace_bytes,
  * ftmi_align_dijkstra, ftmi_align_count, ftmi_attention_score; ftmi_phoneme_features,
- * ftmi_nonzero_moments, ftmi_normalize_nonzero). */
+ * ftmi_nonzero_moments, ftmi_normalize_nonzero; ftmi_embed_bank). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -227,6 +227,31 @@ int ftmi_conv_bank_split(const float *x, int64_t x_stride, int32_t B, int32_t T,
                          const float *bn_scale, const float *bn_shift, float *y,
                          int64_t y_stride, int32_t mma, uint32_t *status, int32_t split_k,
                          float *split_ws, int32_t pool_out, ftmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Conv bank of an EMBEDDED sequence as a table gather (added under ABI 20): the bank of
+ * kernel sizes kmin..kmax (pad k/2, ReLU then BN, as ftmi_conv_bank) applied to
+ * embedding(ids) — the prenet CBHG bank (models/forward_tacotron.py:304-306 feeds it the
+ * embedding; kmin = 1) and a SeriesPredictor's first conv (:31-36,47-49; kmin = kmax = 5).
+ * A convolution of embedding rows is linear in them, so W_k[:, :, j] . E[s] is a constant of
+ * the weights:
+ *   table [num_rows][taps][Cout] fp32, taps ordered (k = kmin..kmax, j = 0..k-1), holds it;
+ *   y[b, t, (k - kmin) Cout + n] = BN_k(relu(sum_{j < k, 0 <= t + j - k/2 < T}
+ *                                            table[ids[b, t + j - k/2]][(k, j)][n]))
+ * summed in tap order in fp32: bit-identical from launch to launch.  Taps outside their own
+ * sequence add nothing; an id outside [0, num_rows) contributes zero (ftmi_embedding's zero
+ * row; reporting it stays that call's job).  bn_scale / bn_shift: [G * Cout], G = kmax - kmin
+ * + 1.  y: (B, T, G * Cout) rows with y_stride floats.  flags: FTMI_BANK_POOL — y receives the
+ * CBHG maxpool(2, 1) of that (y[t] = max(bank[t - 1], bank[t]), y[0] = bank[0]);
+ * FTMI_BANK_Y_SPLIT — y as f16x3 split rows of G * Cout (the operand of
+ * ftmi_conv_args.x_split), a value beyond 65504 in magnitude or not a number sets status
+ * bit 0 (optional word).
+ * kmax <= 16 and Cout % 256 == 0, else FTMI_E_UNSUPPORTED; table / bn / y 16-B aligned.
+ * ---------------------------------------------------------------------------------- */
+int ftmi_embed_bank(const int64_t *ids, int32_t B, int32_t T, const float *table,
+                    int32_t num_rows, int32_t kmin, int32_t kmax, int32_t Cout,
+                    const float *bn_scale, const float *bn_shift, float *y, int64_t y_stride,
+                    int32_t flags, uint32_t *status, ftmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * One highway layer (common_layers.py:22-35):

@@ -4,7 +4,10 @@
         --variant base: --variant halves0:FTMI_BANK_HALVES=0 -- --config c2 --steps 50
 
 A variant is NAME:VAR=VAL,VAR=VAL (empty after the colon: the default environment;
-FTMI_LIB=<path> selects another build).  Each round runs every variant once, in order, as a
+FTMI_LIB=<path> selects another build).  NAME@DIR:... runs the bench.py of another checkout
+(DIR relative to this one, e.g. an export of the parent commit with its own built library)
+instead of this tree's: a change that is not an environment switch is A/B-ed tree against
+tree.  Each round runs every variant once, in order, as a
 child `python bench.py <bench args> --no-cpu-baseline` under its own time limit.  Every
 child's command, environment overrides, exit code, wall time and the tails of its stdout and
 stderr go to the JSONL log whatever happens, and a child that fails — non-zero exit, or no
@@ -24,11 +27,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def parse_variant(spec: str):
     name, _, rest = spec.partition(':')
+    name, _, tree = name.partition('@')
     env = {}
     for kv in filter(None, rest.split(',')):
         k, _, v = kv.partition('=')
         env[k] = v
-    return name, env
+    return name, env, os.path.normpath(os.path.join(ROOT, tree)) if tree else ROOT
 
 
 def main():
@@ -45,15 +49,15 @@ def main():
         args.append('--no-cpu-baseline')
     variants = [parse_variant(v) for v in a.variant]
     os.makedirs(os.path.dirname(a.log), exist_ok=True)
-    cmd = [sys.executable, '-u', os.path.join(ROOT, 'bench.py'), *args]
-    results = {n: [] for n, _ in variants}
+    results = {n: [] for n, _, _ in variants}
     with open(a.log, 'a') as log:
         for r in range(a.rounds):
-            for name, env in variants:
+            for name, env, tree in variants:
+                cmd = [sys.executable, '-u', os.path.join(tree, 'bench.py'), *args]
                 t0 = time.time()
                 try:
                     p = subprocess.run(cmd, env={**os.environ, **env}, capture_output=True,
-                                       text=True, timeout=a.timeout, cwd=ROOT)
+                                       text=True, timeout=a.timeout, cwd=tree)
                     rc, out, err = p.returncode, p.stdout, p.stderr
                 except subprocess.TimeoutExpired as e:
                     rc = 'timeout'
