@@ -152,6 +152,14 @@ SIGNATURES = {
                                       P, P, c_int64, c_int, P, c_float, P, P, P, P]),
     'ftmi_nonzero_moments': (c_int, [P, c_int64, P, P]),
     'ftmi_normalize_nonzero': (c_int, [P, c_int64, c_float, c_float, P]),
+    'ftmi_l1_loss_workspace_bytes': (c_int64, [c_int, c_int, c_int]),
+    'ftmi_l1_loss': (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, c_int64, c_int64, c_int, c_int,
+                             c_int, P, P, P, P]),
+    'ftmi_cross_entropy_workspace_bytes': (c_int64, [c_int64, c_int]),
+    'ftmi_cross_entropy': (c_int, [P, c_int64, c_int64, c_int, P, P, P, P, P]),
+    'ftmi_mol_loss_workspace_bytes': (c_int64, [c_int64, c_int]),
+    'ftmi_mol_loss': (c_int, [P, c_int64, c_int64, c_int, P, ctypes.c_double, ctypes.c_double, P, P,
+                              P, P]),
     'ftmi_mel_nnls': (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P,
                               c_float, c_int, P, P]),
     'ftmi_nnls_lbfgsb_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int, c_int]),

@@ -1229,3 +1229,124 @@ def normalize_nonzero(values: torch.Tensor, mean: float, std: float) -> torch.Te
     launch('ftmi_normalize_nonzero', f'normalize_nonzero[n={n}]', 2.0 * n, 8.0 * n,
            values.data_ptr(), n, float(mean), float(std), _stream())
     return values
+
+
+# ---- Validation losses (csrc/eval.hip) --------------------------------------------------------
+
+_EVAL_WS = {}  # (device, stream) -> uint8 workspace of per-workgroup partials, grown on demand
+
+
+def eval_workspace(nbytes: int, device, what: str) -> torch.Tensor:
+    """The partial-sum workspace of the loss kernels, cached per device and stream (scratch:
+    nothing in it outlives an entry point).  nbytes == 0 is the query's answer for a shape the
+    kernels do not take."""
+    if nbytes <= 0:
+        raise _lib.FtmiError(f'{what}: FTMI_E_UNSUPPORTED (the workspace query returned 0)')
+    dev = torch.device(device)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), _stream())
+    ws = _EVAL_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _EVAL_WS[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return ws
+
+
+def _l1_strides(t: torch.Tensor, name: str) -> Tuple[int, int, int]:
+    """(item, channel, frame) strides of a (B, C, L) operand of ftmi_l1_loss: frame-major or
+    channel-major planes.  A stride of a size-1 dimension is never used, so it is replaced by
+    the one a contiguous tensor would have."""
+    B, C, L = t.shape
+    s_b, s_c, s_t = t.stride()
+    if L == 1:
+        s_t = 1
+    if C == 1:
+        s_c = L if s_t == 1 else 1
+    if B == 1:
+        s_b = 0
+    if s_b < 0 or not ((s_t == 1 and s_c >= L) or (s_c == 1 and s_t >= C)):
+        raise ValueError(f'{name} needs unit frame stride with a channel stride >= L, or unit channel '
+                         f'stride with a frame stride >= C, got shape {tuple(t.shape)} strides '
+                         f'{t.stride()}')
+    return s_b, s_c, s_t
+
+
+def l1_loss(x: torch.Tensor, target: torch.Tensor, lens: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Masked (lens: int32 [B], frames t < lens[b] count) or plain mean |x - target| of two fp32
+    (B, C, L) tensors (ftmi_l1_loss) -> 0-d fp32 on the device, or `out` (one fp32 element)."""
+    _dev(x, target, lens, out)
+    for name, t in (('x', x), ('target', target)):
+        if t.dim() != 3 or t.dtype != _f32 or 0 in t.shape:
+            raise ValueError(f'{name} must be a non-empty (B, C, L) fp32 tensor, got shape '
+                             f'{tuple(t.shape)} {t.dtype}')
+    if x.shape != target.shape or x.device != target.device:
+        raise ValueError(f'x and target must agree in shape and device, got {tuple(x.shape)} and '
+                         f'{tuple(target.shape)}')
+    B, C, L = x.shape
+    xs, ts = _l1_strides(x, 'x'), _l1_strides(target, 'target')
+    if lens is not None and (lens.dtype != torch.int32 or lens.shape != (B,)
+                             or not lens.is_contiguous() or lens.device != x.device):
+        raise ValueError(f'lens must be a contiguous int32 [{B}] tensor on {x.device}')
+    if out is None:
+        out = torch.empty((), device=x.device, dtype=_f32)
+    elif out.dtype != _f32 or out.numel() != 1 or out.device != x.device:
+        raise ValueError('out must hold one fp32 element on the device of x')
+    ws = eval_workspace(int(_lib.load().ftmi_l1_loss_workspace_bytes(B, C, L)), x.device,
+                        f'l1_loss[B={B},C={C},L={L}]')
+    n = float(B) * C * L
+    launch('ftmi_l1_loss', f'l1_loss[B={B},C={C},L={L}]', 3.0 * n, 8.0 * n, x.data_ptr(), *xs,
+           target.data_ptr(), *ts, B, C, L, _ptr(lens), out.data_ptr(), ws.data_ptr(), _stream())
+    return out
+
+
+def _loss_rows(t: torch.Tensor, name: str) -> Tuple[int, int, int]:
+    """(rows, C, ld) of a (rows, C) fp32 matrix with unit column stride and a row stride >= C."""
+    if t.dim() != 2 or t.dtype != _f32 or 0 in t.shape:
+        raise ValueError(f'{name} must be a non-empty (rows, C) fp32 tensor, got shape '
+                         f'{tuple(t.shape)} {t.dtype}')
+    rows, C = t.shape
+    ld = t.stride(0) if rows > 1 else C
+    if (C > 1 and t.stride(1) != 1) or ld < C:
+        raise ValueError(f'{name} needs unit column stride and a row stride >= C, got shape '
+                         f'{tuple(t.shape)} strides {t.stride()}')
+    return rows, C, ld
+
+
+def cross_entropy(logits: torch.Tensor, target: torch.Tensor):
+    """(loss, bad): the mean cross-entropy of fp32 (rows, C) logits against int32 [rows] labels
+    as a 0-d fp32 tensor, and a 0-d int32 count of labels outside [0, C), which add nothing to
+    the sum (ftmi_cross_entropy).  The caller reads `bad` with the loss; nothing syncs here."""
+    _dev(logits, target)
+    rows, C, ld = _loss_rows(logits, 'logits')
+    if (target.dtype != torch.int32 or target.shape != (rows,) or not target.is_contiguous()
+            or target.device != logits.device):
+        raise ValueError(f'target must be a contiguous int32 [{rows}] tensor on {logits.device}')
+    label = f'cross_entropy[rows={rows},C={C}]'
+    ws = eval_workspace(int(_lib.load().ftmi_cross_entropy_workspace_bytes(rows, C)), logits.device,
+                        label)
+    out = torch.empty((), device=logits.device, dtype=_f32)
+    bad = torch.empty((), device=logits.device, dtype=torch.int32)
+    launch('ftmi_cross_entropy', label, 4.0 * rows * C, 4.0 * rows * (C + 1), logits.data_ptr(), ld,
+           rows, C, target.data_ptr(), out.data_ptr(), bad.data_ptr(), ws.data_ptr(), _stream())
+    return out, bad
+
+
+def mol_loss(y_hat: torch.Tensor, y: torch.Tensor, num_classes: float, log_scale_min: float,
+             per_sample: bool = False):
+    """(loss, per_sample or None): the discretized mixture-of-logistics loss of fp32 (rows, 3 K)
+    parameters against fp32 [rows] samples (ftmi_mol_loss): 0-d fp32, and with per_sample the
+    fp32 [rows] values of reduce=False."""
+    _dev(y_hat, y)
+    rows, C, ld = _loss_rows(y_hat, 'y_hat')
+    if C % 3 != 0:
+        raise ValueError(f'y_hat needs 3 K columns, got {C}')
+    if (y.dtype != _f32 or y.shape != (rows,) or not y.is_contiguous() or y.device != y_hat.device):
+        raise ValueError(f'y must be a contiguous fp32 [{rows}] tensor on {y_hat.device}')
+    label = f'mol_loss[rows={rows},K={C // 3}]'
+    ws = eval_workspace(int(_lib.load().ftmi_mol_loss_workspace_bytes(rows, C // 3)), y_hat.device,
+                        label)
+    out = torch.empty((), device=y_hat.device, dtype=_f32)
+    ps = torch.empty(rows, device=y_hat.device, dtype=_f32) if per_sample else None
+    launch('ftmi_mol_loss', label, 60.0 * rows * C, 4.0 * rows * (C + 1 + bool(per_sample)),
+           y_hat.data_ptr(), ld, rows, C, y.data_ptr(), float(num_classes), float(log_scale_min),
+           out.data_ptr(), _ptr(ps), ws.data_ptr(), _stream())
+    return out, ps

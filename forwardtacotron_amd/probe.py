@@ -1,7 +1,8 @@
 """Per-launch kernel timing with HIP events (bench.py's live roofline measurement).
 
 Every ops.* wrapper enqueues exactly one ftmi_* entry point (one kernel; ftmi_rnn_bidir
-adds a 16-byte-aligned workspace memset) on torch's current stream and reports a label
+adds a 16-byte-aligned workspace memset, the losses of csrc/eval.hip a one-workgroup launch
+that combines their partials) on torch's current stream and reports a label
 plus the launch's ALGORITHMIC work: flops (2 per multiply-add of the contraction the
 reference defines) and bytes (each input read once + each output written once).  While a
 KernelProbe is active the launch is bracketed by two torch.cuda.Events on that same

@@ -87,7 +87,8 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * ftmi_griffinlim_iter, ftmi_istft_fused; 20: ftmi_tacotron_decoder[_workspace_bytes];
  * added under 20 without a signature change: ftmi_align_workspace_bytes,
  * ftmi_align_dijkstra, ftmi_align_count, ftmi_attention_score; ftmi_phoneme_features,
- * ftmi_nonzero_moments, ftmi_normalize_nonzero; ftmi_embed_bank). */
+ * ftmi_nonzero_moments, ftmi_normalize_nonzero; ftmi_embed_bank; ftmi_l1_loss,
+ * ftmi_cross_entropy, ftmi_mol_loss and their *_workspace_bytes). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -839,6 +840,61 @@ int ftmi_phoneme_features(const float *mel, int64_t ld_bin, int64_t ld_item, int
                           int32_t *dur_sum, ftmi_stream_t stream);
 int ftmi_nonzero_moments(const float *values, int64_t n, double *out, ftmi_stream_t stream);
 int ftmi_normalize_nonzero(float *values, int64_t n, float mean, float std, ftmi_stream_t stream);
+
+/* ---- Validation losses (the reference's evaluate(): trainer/common.py:69-78 MaskedL1,
+ * F.l1_loss, F.cross_entropy, utils/distribution.py:16-84 discretized_mix_logistic_loss) ----------
+ * Common to the three: every term and every sum is fp64, and the result is rounded to fp32 once.
+ * A first launch gives each workgroup a fixed slice of the input (which slice depends on the shape
+ * alone) and writes one fp64 partial per workgroup into `workspace`; a second launch of one
+ * workgroup adds the partials in a fixed order (1024 strided sums, then a fixed tree) and divides.
+ * No workgroup waits for another and nothing is added with atomics: the same input gives the same
+ * bits on every call.  workspace: ftmi_*_workspace_bytes(...) bytes (0: unsupported shape or bad
+ * sizes), 16-B aligned, one per stream; it need not be zeroed.  out: one device float.
+ *
+ * ftmi_l1_loss: x, target fp32 (B, C, L), each with its own item / channel / frame strides in
+ *   floats.  Each operand must be frame-major (frame stride 1, channel stride >= L) or
+ *   channel-major (channel stride 1, frame stride >= C), item stride >= 0; else FTMI_E_SHAPE.
+ *   lens: device int32 [B] or NULL.  With lens, n_b = clamp(lens[b], 0, L) and
+ *     out = sum_{b, c, t < n_b} |x - target| / (C * sum_b n_b)          (MaskedL1)
+ *   sum_b n_b == 0 gives NaN, the reference's 0/0.  Elements at t >= n_b are never read, so a NaN
+ *   or Inf in the padding does not reach the result; the reference multiplies by a 0/1 mask and
+ *   would propagate it.  Domain: finite values where t < n_b.  Without lens,
+ *     out = sum |x - target| / (B * C * L)                              (F.l1_loss)
+ *   More than 2^22 workgroups (B * ceil(L / 32)) return FTMI_E_UNSUPPORTED.
+ * ftmi_cross_entropy: logits fp32 (rows, C), row stride ld >= C, 1 <= C <= 65536 (more:
+ *   FTMI_E_UNSUPPORTED); target int32 [rows].
+ *     out = mean over rows of (m + log sum_j exp(x_j - m) - x_target), m the row maximum
+ *   A label outside [0, C) adds nothing to the sum (the mean still divides by rows) and is counted
+ *   in *bad_out (device int32): not a status word, the caller reads it with the loss and rejects
+ *   the result if it is not 0.  Domain: finite logits.
+ * ftmi_mol_loss: y_hat fp32 (rows, channels), row stride ld >= channels, channels = 3 K with
+ *   1 <= K <= 32 (else FTMI_E_UNSUPPORTED): K mixture logits, K means, K log scales.  y fp32
+ *   [rows].  Per row and component, with s = max(log_scale, log_scale_min), c = y - mean,
+ *   i = exp(-s), h = 1 / (num_classes - 1):
+ *     plus_in = i (c + h), min_in = i (c - h), mid_in = i c
+ *     softplus(v) = v > 20 ? v : log1p(exp(v)), sigmoid(v) = 1 / (1 + exp(-v))
+ *     log_prob = y < (float)-0.999 ? plus_in - softplus(plus_in)
+ *              : y > (float)0.999  ? -softplus(min_in)
+ *              : d = sigmoid(plus_in) - sigmoid(min_in), d > 1e-5 ? log(max(d, 1e-12))
+ *              : mid_in - s - 2 softplus(mid_in) - log((num_classes - 1) / 2)
+ *   The two tests on y are fp32 compares against the fp32 constants, as torch makes them.  The
+ *   reference blends these branches with 0/1 masks; for finite operands a select gives the same
+ *   value.  Then log_prob += log_softmax(logits)_k, row value v = the stabilised log-sum-exp over
+ *   the K components; per_sample[row] (optional fp32 [rows]) = -v (reduce=False), out = -mean v.
+ *   A row's per_sample value depends on that row alone. */
+int64_t ftmi_l1_loss_workspace_bytes(int32_t B, int32_t C, int32_t L);
+int ftmi_l1_loss(const float *x, int64_t xs_item, int64_t xs_chan, int64_t xs_frame,
+                 const float *target, int64_t ts_item, int64_t ts_chan, int64_t ts_frame, int32_t B,
+                 int32_t C, int32_t L, const int32_t *lens, float *out, void *workspace,
+                 ftmi_stream_t stream);
+int64_t ftmi_cross_entropy_workspace_bytes(int64_t rows, int32_t C);
+int ftmi_cross_entropy(const float *logits, int64_t ld, int64_t rows, int32_t C,
+                       const int32_t *target, float *out, int32_t *bad_out, void *workspace,
+                       ftmi_stream_t stream);
+int64_t ftmi_mol_loss_workspace_bytes(int64_t rows, int32_t K);
+int ftmi_mol_loss(const float *y_hat, int64_t ld, int64_t rows, int32_t channels, const float *y,
+                  double num_classes, double log_scale_min, float *out, float *per_sample,
+                  void *workspace, ftmi_stream_t stream);
 
 #ifdef __cplusplus
 }
