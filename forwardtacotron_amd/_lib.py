@@ -66,6 +66,27 @@ class NnlsArgs(ctypes.Structure):
                          'active')]
 
 
+CHAIN_EMBEDDING, CHAIN_CONV1D, CHAIN_RNN_BIDIR, CHAIN_ROWDOT = 1, 2, 3, 4
+CHAIN_ALIGN16 = 1
+CHAIN_PTRS, CHAIN_INTS, CHAIN_FLOATS = 12, 16, 2
+
+
+class ChainRef(ctypes.Structure):
+    """Mirror of ftmi_chain_ref (include/ftmi.h)."""
+    _fields_ = [('slot', c_int), ('flags', c_int), ('offset', c_int64), ('bytes', c_int64)]
+
+
+class ChainOp(ctypes.Structure):
+    """Mirror of ftmi_chain_op (include/ftmi.h)."""
+    _fields_ = [('tag', c_int), ('reserved', c_int), ('p', ChainRef * CHAIN_PTRS),
+                ('i', c_int64 * CHAIN_INTS), ('f', c_float * CHAIN_FLOATS)]
+
+
+class ChainBase(ctypes.Structure):
+    """Mirror of ftmi_chain_base (include/ftmi.h)."""
+    _fields_ = [('base', P), ('bytes', c_int64)]
+
+
 # name -> (restype, argtypes); the exact export list of include/ftmi.h
 SIGNATURES = {
     'ftmi_abi_version': (c_int, []),
@@ -114,6 +135,8 @@ SIGNATURES = {
     'ftmi_series_proj_add': (c_int, [P, c_int64, c_int, c_int, c_int, P, P, P, c_float, P, P, P,
                                      c_float, P]),
     'ftmi_rowdot': (c_int, [P, c_int64, c_int64, c_int, P, P, c_float, P, P]),
+    'ftmi_run_chain': (c_int, [ctypes.POINTER(ChainOp), c_int, ctypes.POINTER(ChainBase), c_int,
+                               ctypes.POINTER(c_int), P]),
     'ftmi_embedding_posenc': (c_int, [P, c_int, c_int, P, c_int64, c_int, P, P, P, P, P]),
     'ftmi_lr_posenc': (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, P, P, P, c_int64, P]),
     'ftmi_layernorm': (c_int, [P, c_int64, c_int64, c_int, P, P, c_float, P, c_int64, P]),

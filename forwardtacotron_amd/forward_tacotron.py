@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import chain, ops
 from .common_layers import (CBHG, BatchNormConv, BiRNN, Conv1dParams, LengthRegulator,
                             LinearParams, Packed, pack_conv)
 from .text.symbols import phonemes
@@ -95,7 +95,14 @@ class SeriesPredictor(Packed):
         return self.lin.weight.detach().reshape(-1).contiguous(), self.lin.bias.detach().contiguous()
 
     def forward_bt(self, x: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
-        """(B, T) ids -> (B, T) series (before the reference's trailing unsqueeze)."""
+        """(B, T) ids -> (B, T) series (before the reference's trailing unsqueeze): the whole
+        chain as one launch list (chain.series_predictor; FTMI_CHAIN=0: a launch per op)."""
+        if chain.CHAIN:
+            return chain.series_predictor(self, x, alpha)
+        return self._forward_ops(x, alpha)
+
+    def _forward_ops(self, x: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
+        """forward_bt one launch per op; also the pass a launch list is recorded from."""
         h = ops.embedding(x, self.embedding.weight.detach())
         for conv in self.convs:
             h = conv.forward_cl(h)

@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, probe
 from ._lib import ConvArgs
 from .probe import launch
 
@@ -236,6 +236,16 @@ def _dev(*ts):
                                'tensor); there is no CPU fallback')
 
 
+def _new(*shape, device, dtype=_f32) -> torch.Tensor:
+    """torch.empty for an op's output or workspace; while a launch list is being recorded
+    (chain.py) the recorder notes it, so the plan can lay it out in its one workspace."""
+    t = torch.empty(*shape, device=device, dtype=dtype)
+    r = probe._RECORDER
+    if r is not None:
+        r.allocs.append(t)
+    return t
+
+
 def _rows(x: torch.Tensor) -> Tuple[int, int, int, int]:
     """(B, T, C, row_stride) of a channels-last (B, T, C) view with uniformly strided rows."""
     if x.dim() != 3 or x.stride(2) != 1 or x.stride(0) != x.size(1) * x.stride(1):
@@ -253,7 +263,7 @@ def embedding(ids: torch.Tensor, table: torch.Tensor, err: Optional[torch.Tensor
     if ids.dtype != torch.int64:
         ids = ids.long()
     table = table.contiguous()
-    out = torch.empty(*ids.shape, table.size(1), device=table.device, dtype=_f32)
+    out = _new(*ids.shape, table.size(1), device=table.device)
     n, d = ids.numel(), table.size(1)
     launch('ftmi_embedding', f'embedding[n={n},d={d}]', 0, n * 8 + 2 * n * d * 4,
            ids.data_ptr(), n, table.data_ptr(), table.size(0), d, out.data_ptr(), _ptr(err),
@@ -336,7 +346,7 @@ def conv1d(x: torch.Tensor, w: torch.Tensor, k: int, pad: int, *, bias=None, rel
         raise ValueError(f'packed weight {tuple(w.shape)} does not match k={k}, Cin={Cin}')
     y = None
     if want_y:
-        y = out if out is not None else torch.empty(B, To, N, device=x.device, dtype=_f32)
+        y = out if out is not None else _new(B, To, N, device=x.device)
         _rows(y)
     if residual is not None:
         _rows(residual)
@@ -363,7 +373,7 @@ def conv1d(x: torch.Tensor, w: torch.Tensor, k: int, pad: int, *, bias=None, rel
     else:
         sk = _split_k(M, N, k * Cin, a.mma, _slab(a.mma, T, To, Cin, k, N, M), Cin)
     if sk > 1:
-        part = torch.empty(sk * M * N, device=x.device, dtype=_f32)
+        part = _new(sk * M * N, device=x.device)
         a.split_k, a.split_ws = sk, part.data_ptr()
     label = (f'conv1d[M={M},N={N},K={k * Cin}{",maxpool" if maxpool else ""}'
              f'{",xsplit" if x_split else ""},mma={a.mma}]')
@@ -804,11 +814,11 @@ def rnn_bidir(cell: int, xp: torch.Tensor, H: int, w_hh: torch.Tensor, b_hh: Opt
     _dev(xp, w_hh, b_hh, index, xp_zero, lengths)
     B, T_src, _, xs = _rows(xp)
     T = T if T is not None else T_src
-    y = torch.empty(B, T, 2 * H, device=xp.device, dtype=_f32)
+    y = _new(B, T, 2 * H, device=xp.device)
     lib = _lib.load()
     need = int(lib.ftmi_rnn_workspace_bytes(B, H, cell)) // 4 + 4
     if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=xp.device, dtype=torch.int32)
+        ws = _new(need, device=xp.device, dtype=torch.int32)
     if index is not None:
         assert index.dtype == torch.int32 and index.is_contiguous() and index.shape == (B, T)
     G = 4 if cell else 3
@@ -908,7 +918,7 @@ def rowdot(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], alpha
     """(x . w + bias) / alpha over the last dim: (B, T, C) -> (B, T)."""
     _dev(x, w, bias)
     B, T, C, xs = _rows(x)
-    out = torch.empty(B, T, device=x.device, dtype=_f32)
+    out = _new(B, T, device=x.device)
     launch('ftmi_rowdot', f'rowdot[M={B * T},C={C}]', 2.0 * B * T * C, 4.0 * (B * T * (C + 1) + C),
            x.data_ptr(), xs, B * T, C, w.data_ptr(), _ptr(bias), float(alpha),
            out.data_ptr(), _stream())

@@ -6,7 +6,8 @@ that combines their partials) on torch's current stream and reports a label
 plus the launch's ALGORITHMIC work: flops (2 per multiply-add of the contraction the
 reference defines) and bytes (each input read once + each output written once).  While a
 KernelProbe is active the launch is bracketed by two torch.cuda.Events on that same
-stream, so elapsed_time() is that kernel's device duration.
+stream, so elapsed_time() is that kernel's device duration.  A launch list (chain.py:
+ftmi_run_chain) is one entry: its ops' summed work, bracketed as a whole.
 """
 from __future__ import annotations
 
@@ -53,7 +54,13 @@ class KernelProbe:
         return out
 
 
+_RECORDER = None  # chain.Recorder while a launch list is being built (chain.py)
+
+
 def launch(name: str, label: str, flops: float, nbytes: float, *args) -> None:
+    r = _RECORDER
+    if r is not None:
+        r.launches.append((name, label, float(flops), float(nbytes), args))
     p = _ACTIVE
     if p is None:
         call(name, *args)

@@ -88,7 +88,7 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * added under 20 without a signature change: ftmi_align_workspace_bytes,
  * ftmi_align_dijkstra, ftmi_align_count, ftmi_attention_score; ftmi_phoneme_features,
  * ftmi_nonzero_moments, ftmi_normalize_nonzero; ftmi_embed_bank; ftmi_l1_loss,
- * ftmi_cross_entropy, ftmi_mol_loss and their *_workspace_bytes). */
+ * ftmi_cross_entropy, ftmi_mol_loss and their *_workspace_bytes; ftmi_run_chain). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -430,6 +430,58 @@ int ftmi_series_proj_add(float *x, int64_t x_stride, int32_t B, int32_t T, int32
  * ---------------------------------------------------------------------------------- */
 int ftmi_rowdot(const float *x, int64_t x_stride, int64_t M, int32_t C, const float *w,
                 const float *bias, float alpha, float *out, ftmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Launch lists (added under ABI 20): a chain of the launches above issued by ONE call, so
+ * the host pays one foreign call per chain instead of one per kernel.  The caller builds the
+ * list once per shape and reuses it from call to call with only the bases patched.
+ *
+ * An op is a tagged record.  Every pointer argument is a reference into a base table:
+ * (slot, byte offset, byte extent); slot < 0 is a NULL pointer.  The extent is the range the
+ * op may touch from that pointer on; FTMI_CHAIN_ALIGN16 demands a 16-byte aligned address.
+ * The integer / float arguments of the entry point travel in i[] / f[] in the order below
+ * (the entry point's own argument order, pointers left out):
+ *   FTMI_CHAIN_EMBEDDING  p: ids, table, out, err          i: n, num_rows, dim
+ *   FTMI_CHAIN_CONV1D     p: x, w, bias, bn_scale, bn_shift, residual, y, yt, split_ws,
+ *                            w_split, status
+ *                         i: x_stride, B, T, Cin, N, k, pad, relu, maxpool, res_stride,
+ *                            y_stride, T_out, mma, split_k, x_split
+ *   FTMI_CHAIN_RNN_BIDIR  p: xp, index, xp_zero, w_hh, b_hh, lengths, y, status, sync
+ *                         i: cell, B, T, H, xp_stride, T_src, y_stride, mma   f: pad_value
+ *   FTMI_CHAIN_ROWDOT     p: x, w, bias, out               i: x_stride, M, C   f: alpha
+ *
+ * ftmi_run_chain first validates the whole list and launches nothing unless it passes:
+ * n > 0, every tag known, every slot inside the table with a non-NULL base, every
+ * [offset, offset + extent) inside its slot's declared size, every flagged address aligned,
+ * and every range an op WRITES (conv y / yt / split_ws, recurrence y / sync, embedding out,
+ * rowdot out) at least as large as the op's shape needs.  A failure returns
+ * FTMI_E_ARG (FTMI_E_ALIGN for alignment) with *failed_op = the offending op (-1: the list
+ * itself).  Then the ops run in order through the entry points above on `stream`; the first
+ * non-zero return stops the list and is returned with *failed_op = that op's index (earlier
+ * ops stay queued).  No synchronisation, no allocation, no state of its own: safe on several
+ * streams at once and inside stream capture.  failed_op may be NULL.
+ * ---------------------------------------------------------------------------------- */
+enum { FTMI_CHAIN_EMBEDDING = 1, FTMI_CHAIN_CONV1D = 2, FTMI_CHAIN_RNN_BIDIR = 3,
+       FTMI_CHAIN_ROWDOT = 4 };
+enum { FTMI_CHAIN_ALIGN16 = 1 };
+enum { FTMI_CHAIN_PTRS = 12, FTMI_CHAIN_INTS = 16, FTMI_CHAIN_FLOATS = 2 };
+typedef struct ftmi_chain_ref {
+  int32_t slot;  /* index into the base table, < 0: NULL */
+  int32_t flags; /* FTMI_CHAIN_ALIGN16 */
+  int64_t offset, bytes;
+} ftmi_chain_ref;
+typedef struct ftmi_chain_op {
+  int32_t tag, reserved;
+  ftmi_chain_ref p[FTMI_CHAIN_PTRS];
+  int64_t i[FTMI_CHAIN_INTS];
+  float f[FTMI_CHAIN_FLOATS];
+} ftmi_chain_op;
+typedef struct ftmi_chain_base {
+  void *base;    /* device address of the slot (ids, a packed weight, workspace, output ...) */
+  int64_t bytes; /* its declared size */
+} ftmi_chain_base;
+int ftmi_run_chain(const ftmi_chain_op *ops, int32_t n, const ftmi_chain_base *bases,
+                   int32_t n_bases, int32_t *failed_op, ftmi_stream_t stream);
 
 /* ====================================================================================
  * Audio path: utils/dsp.py (DSP.wav_to_mel :71-87, griffinlim :89-103), whose arithmetic
