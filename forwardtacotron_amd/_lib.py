@@ -21,7 +21,7 @@ _lib = None
 
 c_int, c_int64, c_float, c_void_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 P = c_void_p  # every device pointer travels as void*
-ABI_VERSION = 20
+ABI_VERSION = 21
 MMA_F32, MMA_BF16X6, MMA_F16X3 = 0, 1, 2
 
 
@@ -35,6 +35,20 @@ class ConvArgs(ctypes.Structure):
         ('y', P), ('y_stride', c_int64), ('yt', P), ('T_out', c_int), ('mma', c_int),
         ('split_k', c_int), ('split_ws', P), ('w_split', P), ('status', P), ('x_split', c_int),
     ]
+
+
+class GemmRoute(ctypes.Structure):
+    """Mirror of ftmi_gemm_route (include/ftmi.h): the kernel a conv / bank / highway launch
+    takes, the split it requires and that split's workspace floats."""
+    _fields_ = [('kernel', c_int), ('split_k', c_int), ('ws_floats', c_int64), ('pooled', c_int),
+                ('band', c_int)]
+
+
+# include/ftmi.h FTMI_ROUTE_*
+(ROUTE_UNSUPPORTED, ROUTE_SKINNY, ROUTE_SKINNY_BANK, ROUTE_SLAB, ROUTE_SLAB_WS, ROUTE_SLAB_PF,
+ ROUTE_BANK_WALK, ROUTE_BANK_HALVES, ROUTE_X6B_F16, ROUTE_X6B_BF16, ROUTE_X6, ROUTE_F32) = range(12)
+ROUTE_SKINNIES = (ROUTE_SKINNY, ROUTE_SKINNY_BANK)
+ROUTE_SLABS = (ROUTE_SLAB, ROUTE_SLAB_WS, ROUTE_SLAB_PF, ROUTE_BANK_WALK)
 
 
 class WaveRNNArgs(ctypes.Structure):
@@ -107,6 +121,12 @@ SIGNATURES = {
     'ftmi_highway': (c_int, [P, c_int64, c_int64, c_int, P, P, P, P, P, c_int64, c_int, P, P]),
     'ftmi_highway_split': (c_int, [P, c_int64, c_int64, c_int, P, P, P, P, P, c_int64, c_int, P,
                                    c_int, P, P]),
+    'ftmi_conv1d_route': (c_int, [ctypes.POINTER(ConvArgs), ctypes.POINTER(GemmRoute)]),
+    'ftmi_conv_bank_route': (c_int, [P, c_int64, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P,
+                                     c_int64, c_int, P, c_int, ctypes.POINTER(GemmRoute)]),
+    'ftmi_highway_route': (c_int, [P, c_int64, c_int64, c_int, P, P, P, P, P, c_int64, c_int, P,
+                                   ctypes.POINTER(GemmRoute)]),
+    'ftmi_gemm_switches_digest': (ctypes.c_uint64, []),
     'ftmi_highway_stack': (c_int, [P, c_int64, c_int64, c_int, c_int, P, c_int, P, P, P, P, P,
                                    c_int, P, c_int64, P, c_int64, P, P]),
     'ftmi_highway_stack_spread_ws_bytes': (c_int64, [c_int64]),

@@ -244,15 +244,12 @@ def _base(t: torch.Tensor):
     return t.data_ptr(), t.numel() * t.element_size()
 
 
-_ENV = ('FTMI_GEMM_SKINNY', 'FTMI_SKINNY_CPB', 'FTMI_GEMM_SLAB_MIN')
-
-
 def policy_key():
     """Everything besides the shape and the weights that the per-op path's choices read: a
-    change of any builds another plan."""
-    env = os.environ.get
+    change of any builds another plan.  The library's routing switches enter as its own
+    digest of them (ftmi_gemm_switches_digest), so none is listed here."""
     return (ops.MMA, ops.RNN_MMA, ops._FORCED[-1] if ops._FORCED else None, bool(ops._COMPACT),
-            ops.SLAB, ops.SLAB_K1_NMIN, *[env(k) for k in _ENV])
+            _lib.load().ftmi_gemm_switches_digest())
 
 
 def _plans(mod, pack_key):

@@ -38,7 +38,13 @@
 // < 2^-22 relative.  The only range limit is |a| < 65504 for the activations: an overflow
 // makes the accumulator non-finite, which the epilogue reports through *status (bit 0);
 // the model layer then recomputes the call on the fp32 path.
+#include <stddef.h>
+#include <stdlib.h>
+#include <string.h>
+
 #include "common.h"
+
+extern char **environ;
 
 namespace {
 
@@ -541,217 +547,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const GemmParams p
     }
   }
 }
-
-// ---------------------------------------------------------------------------------------
-// bf16x6, software-pipelined variant ("x6p"): ONE workgroup per CU (4 waves, one per SIMD),
-// LDS double-buffered (2 x 72 KB).  In iteration k each wave reads chunk k's fragments from
-// buffer k&1, and between its MFMAs splits chunk k+1 (already in registers) into buffer
-// (k+1)&1; chunk k+2's global loads are issued at the top of the iteration into the register
-// set chunk k+1 just vacated (two register sets, loop unrolled by two so every index is
-// static).  One barrier per chunk.
-template <int EPI, bool MAXPOOL>
-__global__ __launch_bounds__(256, 1) void conv_gemm_x6p_kernel(const GemmParams p) {
-  __shared__ __attribute__((aligned(16))) __bf16 lds[2 * 2 * 3 * X6_PIECE];
-
-  const int tile = blockIdx.x;
-  int gi = 0;
-  while (gi + 1 < p.ngroups && tile >= p.g[gi + 1].tile0) ++gi;
-  const GemmGroup &G = p.g[gi];
-  const int lt = tile - G.tile0;
-  const int mt = lt / G.ntiles;
-  const int nt = lt - mt * G.ntiles;
-  const int m0 = mt * BM, n0 = nt * BN;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-
-  const int lr = tid >> 3, lc = tid & 7;
-  const float *arow[4];
-  int at[4];
-  bool aok[4], bok[4];
-  const float *wrow[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int m = m0 + lr + 32 * q;
-    aok[q] = m < p.M;
-    const int mm = aok[q] ? m : 0;
-    const int b = mm / p.To;
-    at[q] = mm - b * p.To;
-    arow[q] = p.x + (int64_t)b * p.T * p.x_stride;
-    const int n = n0 + lr + 32 * q;
-    bok[q] = n < G.N;
-    wrow[q] = G.w + (int64_t)(bok[q] ? n : 0) * G.Ktot;
-  }
-  int nk = (G.Ktot + X6_BK - 1) / X6_BK;
-  int kc0 = 0;
-  if (p.split > 1) {
-    kc0 = blockIdx.y * p.kc_per;
-    nk = min(nk - kc0, p.kc_per);
-  }
-  int kk = kc0 * X6_BK + 4 * lc, tj = kk / p.Cin, tc = kk - tj * p.Cin;
-
-  auto gload = [&](f32x4 (&ra)[4], f32x4 (&rb)[4]) {
-    const bool kok = kk < G.Ktot;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int ts = at[q] + tj - G.pad;
-      const bool ok = kok && aok[q] && ts >= 0 && ts < p.T;
-      const float *src = arow[q] + (int64_t)(ok ? ts : 0) * p.x_stride + (ok ? tc : 0);
-      f32x4 v = *(const f32x4 *)src;
-      if (MAXPOOL) {
-        const bool okp = ok && ts > 0;
-        v = fmax4(v, *(const f32x4 *)(src - (okp ? p.x_stride : 0)));
-      }
-      ra[q] = sel4(ok, v);
-      rb[q] = sel4(kok && bok[q], *(const f32x4 *)(wrow[q] + (kok ? kk : 0)));
-    }
-    kk += X6_BK;
-    tc += X6_BK;
-    while (tc >= p.Cin) {
-      tc -= p.Cin;
-      ++tj;
-    }
-  };
-  auto split_store = [&](__bf16 *base, int q, f32x4 va, f32x4 vb) {
-    const int off = (lr + 32 * q) * X6_STRIDE + 4 * lc;
-    bf16x4 h1, h2, h3;
-    split3(va, h1, h2, h3);
-    *(bf16x4 *)(base + 0 * X6_PIECE + off) = h1;
-    *(bf16x4 *)(base + 1 * X6_PIECE + off) = h2;
-    *(bf16x4 *)(base + 2 * X6_PIECE + off) = h3;
-    split3(vb, h1, h2, h3);
-    *(bf16x4 *)(base + 3 * X6_PIECE + off) = h1;
-    *(bf16x4 *)(base + 4 * X6_PIECE + off) = h2;
-    *(bf16x4 *)(base + 5 * X6_PIECE + off) = h3;
-  };
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int fr = lane & 15, fk = 8 * (lane >> 4);
-  // MFMAs on buffer `cur`, interleaved with staging the next chunk into `nxt`
-  auto step = [&](const __bf16 *cur, __bf16 *nxt, bool stage, const f32x4 (&ra)[4],
-                  const f32x4 (&rb)[4]) {
-    bf16x8 b[4][3];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int pc = 0; pc < 3; ++pc)
-        b[ni][pc] = *(const bf16x8 *)(cur + (3 + pc) * X6_PIECE + (wn * 64 + ni * 16 + fr) * X6_STRIDE + fk);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      bf16x8 a[3];
-#pragma unroll
-      for (int pc = 0; pc < 3; ++pc)
-        a[pc] = *(const bf16x8 *)(cur + pc * X6_PIECE + (wm * 64 + mi * 16 + fr) * X6_STRIDE + fk);
-      if (stage) split_store(nxt, mi, ra[mi], rb[mi]);
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        f32x4 c = acc[mi][ni];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[ni][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[ni][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[ni][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[ni][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[ni][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[ni][0], c, 0, 0, 0);
-        acc[mi][ni] = c;
-      }
-    }
-  };
-
-  __bf16 *buf0 = lds, *buf1 = lds + 2 * 3 * X6_PIECE;
-  f32x4 ra0[4], rb0[4], ra1[4], rb1[4];
-  // prologue: chunk 0 -> buf0, chunk 1 -> registers set 1
-  gload(ra0, rb0);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) split_store(buf0, q, ra0[q], rb0[q]);
-  if (nk > 1) gload(ra1, rb1);
-  __syncthreads();
-  int kc = 0;
-  for (; kc + 1 < nk; kc += 2) {
-    // even iteration: compute buf0 (chunk kc), stage chunk kc+1 (set 1) into buf1
-    if (kc + 2 < nk) gload(ra0, rb0);
-    step(buf0, buf1, true, ra1, rb1);
-    __syncthreads();
-    // odd iteration: compute buf1 (chunk kc+1), stage chunk kc+2 (set 0) into buf0
-    if (kc + 3 < nk) gload(ra1, rb1);
-    step(buf1, buf0, kc + 2 < nk, ra0, rb0);
-    __syncthreads();
-  }
-  if (kc < nk) step(buf0, buf1, false, ra1, rb1);  // odd chunk count: last chunk in buf0
-
-  if (p.split > 1) {  // raw partial sums; the epilogue runs in splitk_epilogue_kernel
-    float *part = p.part + (size_t)blockIdx.y * p.M * G.N;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      const int col = n0 + wn * 64 + ni * 16 + (lane & 15);
-      if (col >= G.N) continue;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int row = m0 + wm * 64 + mi * 16 + 4 * (lane >> 4) + i;
-          if (row < p.M) part[(size_t)row * G.N + col] = acc[mi][ni][i];
-        }
-    }
-    return;
-  }
-
-  // epilogue: tile (mi, ni) element (row 4*(lane>>4) + i, col lane & 15)
-  const int er = 4 * (lane >> 4);
-  if constexpr (EPI == EPI_CONV) {
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      const int col = n0 + wn * 64 + ni * 16 + fr;
-      if (col >= G.N) continue;
-      const float bias = G.bias ? G.bias[col] : 0.f;
-      const float sc = G.scale ? G.scale[col] : 1.f;
-      const float sh = G.scale ? G.shift[col] : 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int row = m0 + wm * 64 + mi * 16 + er + i;
-          if (row >= p.M) continue;
-          float v = acc[mi][ni][i];
-          if (G.bias) v += bias;
-          if (p.relu) v = fmaxf(v, 0.f);
-          if (G.scale) v = v * sc + sh;
-          if (p.residual) v += p.residual[(int64_t)row * p.res_stride + col];
-          if (p.y) p.y[(int64_t)row * p.y_stride + G.ycol0 + col] = v;
-          if (p.yt) {
-            const int b = row / p.To, t = row - b * p.To;
-            p.yt[((int64_t)b * p.yt_channels + G.ycol0 + col) * p.To + t] = v;
-          }
-        }
-    }
-  } else {
-    // packed column blocks of 32: tiles ni = 0,1 are W1 columns, ni = 2,3 the matching W2
-    if (n0 + wn * 64 >= G.N) return;
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      const int col = (n0 + wn * 64) / 2 + ni * 16 + fr;
-      const float b1 = p.b1[col], b2 = p.b2[col];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int row = m0 + wm * 64 + mi * 16 + er + i;
-          if (row >= p.M) continue;
-          const float x1 = acc[mi][ni][i] + b1;
-          const float x2 = acc[mi][ni + 2][i] + b2;
-          const float g = ftmi_sigmoid(x2);
-          const float xin = p.x[(int64_t)row * p.x_stride + col];
-          p.y[(int64_t)row * p.y_stride + col] = highway_mix(g, x1, xin);
-        }
-    }
-  }
-}
-
 
 // ---------------------------------------------------------------------------------------
 // bf16x6 with PRE-SPLIT weights ("x6b", used when the caller passes w_split).  The 4 waves
@@ -3902,47 +3697,93 @@ __global__ __launch_bounds__(512) void panel_proj_kernel(const PanelParams p) {
   if (!(amax <= 65504.f) && p.status) atomicOr(p.status, 1u);
 }
 
-static int x6_variant() {
-  static const int v = [] {
-    const char *e = getenv("FTMI_GEMM_X6");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
+// ---------------------------------------------------------------------------------------
+// Kernel selection.  read_switches() reads every routing switch, per call, into one struct;
+// route() decides the kernel family of a launch from its GemmParams and that struct alone
+// (no launch, no device); launch() issues what route() decided, and the ftmi_*_route queries
+// hand the same decision to a caller that sizes a workspace before it launches.
+
+// Every field an int64_t (the digest hashes the bytes before `digest`: no padding), one
+// line of SWITCHES each: a switch added here is in ftmi_gemm_switches_digest without more.
+struct Switches {
+  int64_t slab;           // FTMI_GEMM_SLAB=0: slab-eligible convolutions on the x6b kernel (A/B timing)
+  int64_t slab_min;       // FTMI_GEMM_SLAB_MIN (MACs): smaller contractions stay on the x6b kernel
+  int64_t slab_ws;        // FTMI_GEMM_SLAB_WS=0/1 forces the 512- / 768-thread slab kernel
+  int64_t slab_k1_nmin;   // FTMI_SLAB_K1_NMIN: narrowest k = 1 GEMM on the slab kernels
+  int64_t slab_pf;        // FTMI_SLAB_PF: 0 = never, 1 = every slab launch without input pooling
+  int64_t slab_band;      // FTMI_SLAB_BAND: column-band tile order, 0 = the row-tile order
+  int64_t skinny;         // FTMI_GEMM_SKINNY=0 turns the skinny kernel off
+  int64_t skinny_cpb;     // FTMI_SKINNY_CPB: 32-channel chunks per skinny block (1 .. SK_CPB; A/B runs)
+  int64_t bank_balanced;  // FTMI_BANK_BALANCED=0: a skinny bank on the one-group-per-block schedule
+  int64_t bank_walk;      // FTMI_BANK_WALK: 0 = never, 1 = at any size
+  int64_t bank_halves;    // FTMI_BANK_HALVES=0: the few-row bank on the skinny kernel + finish
+  uint64_t digest;        // FNV-1a of the fields above
+};
+struct SwitchDef {
+  const char *name;
+  int64_t Switches::*field;
+  int64_t def;  // -1: the kernel's own rule (slab_kernel, bank_walk_ok)
+};
+// column bands of 2 (slab_tile): tools/gemm_one.py under rocprofv3, band 0 -> 2: c5 FFN conv
+// 1179 -> 1147 us (L2->fabric reads 913 -> 662 MB per launch), c3 prenet bank 803 -> 713,
+// postnet bank 710 -> 683, LSTM input projection 305 -> 297; proj1 (2 column tiles) unchanged.
+// FTMI_GEMM_SLAB_MIN = 0: taking the slab for every eligible shape measured fastest on c3
+// (10.01 vs 10.19 ms/step with an 8 GMAC bar); tests use it to cover both kernels.
+const SwitchDef SWITCHES[] = {
+    {"FTMI_GEMM_SLAB", &Switches::slab, 1},
+    {"FTMI_GEMM_SLAB_MIN", &Switches::slab_min, 0},
+    {"FTMI_GEMM_SLAB_WS", &Switches::slab_ws, -1},
+    {"FTMI_SLAB_K1_NMIN", &Switches::slab_k1_nmin, SL_BN},
+    {"FTMI_SLAB_PF", &Switches::slab_pf, -1},
+    {"FTMI_SLAB_BAND", &Switches::slab_band, 2},
+    {"FTMI_GEMM_SKINNY", &Switches::skinny, 1},
+    {"FTMI_SKINNY_CPB", &Switches::skinny_cpb, SK_CPB},
+    {"FTMI_BANK_BALANCED", &Switches::bank_balanced, 1},
+    {"FTMI_BANK_WALK", &Switches::bank_walk, -1},
+    {"FTMI_BANK_HALVES", &Switches::bank_halves, 1},
+};
+
+// One pass over the environment (a launch costs one scan, not a getenv per switch)
+static Switches read_switches() {
+  Switches sw = {};
+  for (const SwitchDef &d : SWITCHES) sw.*d.field = d.def;
+  for (char **e = environ; e && *e; ++e) {
+    if (strncmp(*e, "FTMI_", 5) != 0) continue;
+    const char *eq = strchr(*e, '=');
+    if (!eq) continue;
+    const size_t n = (size_t)(eq - *e);
+    for (const SwitchDef &d : SWITCHES)
+      if (strlen(d.name) == n && strncmp(*e, d.name, n) == 0) sw.*d.field = atoll(eq + 1);
+  }
+  sw.digest = 0xcbf29ce484222325ull;
+  for (size_t i = 0; i < offsetof(Switches, digest); ++i)
+    sw.digest = (sw.digest ^ ((const unsigned char *)&sw)[i]) * 0x100000001b3ull;
+  return sw;
 }
 
-// FTMI_GEMM_SLAB=0 routes the slab-eligible convolutions to the x6b kernel (A/B timing)
-static bool slab_enabled() {
-  static const bool v = [] {
-    const char *e = getenv("FTMI_GEMM_SLAB");
-    return !(e && atoi(e) == 0);
-  }();
-  return v;
-}
+// What route() decides: the kernel family (FTMI_ROUTE_*), the split that family requires with
+// the floats of split_ws that go with it (0: none required — the kernel takes whatever split
+// its caller chose), and whether the pooled / split-row store asked for is accepted.
+struct Route {
+  int kernel;
+  int split;
+  int64_t ws_floats;
+  bool pooled;
+  bool drop_split;  // the caller's split is not used (banks and highway layers off the skinny kernel)
+  int band;         // slab kernels: the column-band tile order (slab_tile)
+};
 
 // slab kernel eligibility: same-length output, Cin % 16 == 0, k taps within the slab halo,
 // groups of equal width (conv bank), 32-bit activation offsets; a k = 1 GEMM only from one
 // whole column tile (N >= 128: the FastPitch predictors' N = 128 projections 23.3 -> 17.2
 // us at 12,800 rows; narrower Linear layers, N = 80, run faster on the 128 x 128 x6b tiles).
-// FTMI_GEMM_SLAB_MIN (MACs, read per call; default 0) keeps smaller contractions on the
-// x6b kernel: tests use it to cover both kernels, A/B runs to size the choice (taking
-// the slab for every eligible shape measured fastest on c3: 10.01 vs 10.19 ms/step with
-// an 8 GMAC bar)
-constexpr int64_t SL_MIN_MACS = 0;
-static int64_t slab_min_macs() {
-  const char *e = getenv("FTMI_GEMM_SLAB_MIN");
-  return e ? atoll(e) : SL_MIN_MACS;
-}
 static bool al16(const void *q) { return ((uintptr_t)q & 15u) == 0; }
-static bool slab_ok(const GemmParams &p, int epi) {
+static bool slab_ok(const GemmParams &p, int epi, const Switches &sw) {
   const GemmGroup &g = p.g[0];
   int64_t macs = 0;
   for (int i = 0; i < p.ngroups; ++i) macs += (int64_t)p.M * p.g[i].N * p.g[i].Ktot;
-  static const int nmin = [] {  // FTMI_SLAB_K1_NMIN: narrowest k = 1 GEMM on the slab kernels
-    const char *e = getenv("FTMI_SLAB_K1_NMIN");
-    return e ? atoi(e) : SL_BN;
-  }();
-  if (!(slab_enabled() && p.To == p.T && p.Cin % 16 == 0 && (g.k > 1 || g.N >= nmin) &&
-        macs >= slab_min_macs() && (int64_t)p.M * p.x_stride < ((int64_t)1 << 31)))
+  if (!(sw.slab != 0 && p.To == p.T && p.Cin % 16 == 0 && (g.k > 1 || g.N >= sw.slab_k1_nmin) &&
+        macs >= sw.slab_min && (int64_t)p.M * p.x_stride < ((int64_t)1 << 31)))
     return false;
   if (p.ngroups > 1 && p.split_req > 1) return false;  // the split-K finish is single-group
   for (int i = 0; i < p.ngroups; ++i) {
@@ -3957,29 +3798,42 @@ static bool slab_ok(const GemmParams &p, int epi) {
   return true;
 }
 
-// The warp-specialised slab kernel (768 threads) for multi-tap convolutions and banks,
-// where the slab split is most of the staging work (measured 7-14 % faster at c3 shapes);
-// the 512-thread form for k = 1 (equal or faster there).  FTMI_GEMM_SLAB_WS=0/1 forces one.
-static bool slab_ws(const GemmParams &p) {
-  static const int v = [] {
-    const char *e = getenv("FTMI_GEMM_SLAB_WS");
-    return e ? atoi(e) : -1;
-  }();
-  return v < 0 ? (p.g[0].k > 1 || p.ngroups > 1) : v != 0;
+// Which slab kernel.  The fragment-prefetch kernel for single-group k = 1 GEMMs (LSTM / GRU
+// input projections: 6-10 % faster than the 512-thread slab kernel); multi-tap convolutions
+// and banks keep the warp-specialised kernel (the prefetch kernel stages in its MFMA waves,
+// ~200 VALU per 48 MFMAs, and measured 4-6 % slower there: DESIGN.md section 4).  The
+// warp-specialised kernel (768 threads) for multi-tap convolutions and banks, where the slab
+// split is most of the staging work (measured 7-14 % faster at c3 shapes); the 512-thread
+// form for k = 1 (equal or faster there).
+static void take_slab(Route &r, const GemmParams &p, bool maxpool, const Switches &sw) {
+  const bool pf = sw.slab_pf < 0 ? p.ngroups == 1 && p.g[0].k == 1 : sw.slab_pf != 0;
+  const bool ws = sw.slab_ws < 0 ? p.g[0].k > 1 || p.ngroups > 1 : sw.slab_ws != 0;
+  r.kernel = !maxpool && pf ? FTMI_ROUTE_SLAB_PF : ws ? FTMI_ROUTE_SLAB_WS : FTMI_ROUTE_SLAB;
+  r.band = (int)sw.slab_band;
 }
 
-// The fragment-prefetch slab kernel for single-group k = 1 GEMMs (LSTM / GRU input
-// projections: 6-10 % faster than the 512-thread slab kernel); multi-tap convolutions and
-// banks keep the warp-specialised kernel (the prefetch kernel stages in its MFMA waves,
-// ~200 VALU per 48 MFMAs, and measured 4-6 % slower there: DESIGN.md section 4).
-// FTMI_SLAB_PF (read per call): 0 = never, 1 = every slab launch without input pooling.
-static bool slab_pf_enabled(const GemmParams &p) {
-  const char *e = getenv("FTMI_SLAB_PF");
-  if (e) return atoi(e) != 0;
-  return p.ngroups == 1 && p.g[0].k == 1;
+// the split-K finish of the slab and 128 x 128 tile kernels (single group)
+static int launch_splitk_finish(const GemmParams &p, hipStream_t s) {
+  const int64_t total = (int64_t)p.M * p.g[0].N;
+  const int eb = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(eb), dim3(256), 0, s, p);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
 }
 
-static int launch_slab(const GemmParams &p, int epi, bool maxpool, hipStream_t s) {
+// The <EPI, MAXPOOL, ...> instantiation of a conv kernel for (epi, maxpool) in scope (the
+// highway epilogue never pools its input); further template arguments follow p_.
+#define FTMI_LAUNCH_EPI(KERNEL_, grid_, block_, p_, ...)                                        \
+  do {                                                                                          \
+    if (epi == EPI_HIGHWAY)                                                                     \
+      hipLaunchKernelGGL((KERNEL_<EPI_HIGHWAY, false, ##__VA_ARGS__>), grid_, block_, 0, s, p_); \
+    else if (maxpool)                                                                           \
+      hipLaunchKernelGGL((KERNEL_<EPI_CONV, true, ##__VA_ARGS__>), grid_, block_, 0, s, p_);     \
+    else                                                                                        \
+      hipLaunchKernelGGL((KERNEL_<EPI_CONV, false, ##__VA_ARGS__>), grid_, block_, 0, s, p_);    \
+  } while (0)
+
+static int launch_slab(const GemmParams &p, int epi, bool maxpool, const Route &r, hipStream_t s) {
   GemmParams q = p;
   const int nch = (q.Cin + 31) / 32;
   q.split = 1;
@@ -3990,12 +3844,7 @@ static int launch_slab(const GemmParams &p, int epi, bool maxpool, hipStream_t s
   }();
   q.diag = diag;
 #endif
-  // column bands of 2 (slab_tile): tools/gemm_one.py under rocprofv3, band 0 -> 2: c5 FFN conv
-  // 1179 -> 1147 us (L2->fabric reads 913 -> 662 MB per launch), c3 prenet bank 803 -> 713,
-  // postnet bank 710 -> 683, LSTM input projection 305 -> 297; proj1 (2 column tiles)
-  // unchanged.  FTMI_SLAB_BAND (read per call) overrides, 0 = the row-tile order.
-  const char *be = getenv("FTMI_SLAB_BAND");
-  q.band = be ? atoi(be) : 2;
+  q.band = r.band;
   q.kc_per = nch;
   if (p.split_req > 1 && p.part) {  // split over channel chunks, no empty splits
     q.kc_per = (nch + p.split_req - 1) / p.split_req;
@@ -4004,44 +3853,26 @@ static int launch_slab(const GemmParams &p, int epi, bool maxpool, hipStream_t s
   const int TS = q.pool_out ? SL_BM - 1 : SL_BM;
   const int MT = (q.M + TS - 1) / TS;
   const int nblk = (MT < 8 ? MT : (MT + 7) / 8 * 8) * q.ngroups * q.g[0].ntiles;  // whole XCD rounds
-  dim3 grid(nblk, q.split), block(512);
-  if (!maxpool && slab_pf_enabled(q)) {
+  const dim3 grid(nblk, q.split);
+  if (r.kernel == FTMI_ROUTE_SLAB_PF) {
     if (epi == EPI_HIGHWAY)
-      hipLaunchKernelGGL(conv_gemm_slabp_kernel<EPI_HIGHWAY>, grid, block, 0, s, q);
+      hipLaunchKernelGGL(conv_gemm_slabp_kernel<EPI_HIGHWAY>, grid, dim3(512), 0, s, q);
     else
-      hipLaunchKernelGGL(conv_gemm_slabp_kernel<EPI_CONV>, grid, block, 0, s, q);
-  } else if (slab_ws(q)) {
-    block = dim3(768);
-    if (epi == EPI_HIGHWAY)
-      hipLaunchKernelGGL((conv_gemm_slab_kernel<EPI_HIGHWAY, false, true>), grid, block, 0, s, q);
-    else if (maxpool)
-      hipLaunchKernelGGL((conv_gemm_slab_kernel<EPI_CONV, true, true>), grid, block, 0, s, q);
-    else
-      hipLaunchKernelGGL((conv_gemm_slab_kernel<EPI_CONV, false, true>), grid, block, 0, s, q);
+      hipLaunchKernelGGL(conv_gemm_slabp_kernel<EPI_CONV>, grid, dim3(512), 0, s, q);
+  } else if (r.kernel == FTMI_ROUTE_SLAB_WS) {
+    FTMI_LAUNCH_EPI(conv_gemm_slab_kernel, grid, dim3(768), q, true);
   } else {
-    if (epi == EPI_HIGHWAY)
-      hipLaunchKernelGGL((conv_gemm_slab_kernel<EPI_HIGHWAY, false, false>), grid, block, 0, s, q);
-    else if (maxpool)
-      hipLaunchKernelGGL((conv_gemm_slab_kernel<EPI_CONV, true, false>), grid, block, 0, s, q);
-    else
-      hipLaunchKernelGGL((conv_gemm_slab_kernel<EPI_CONV, false, false>), grid, block, 0, s, q);
+    FTMI_LAUNCH_EPI(conv_gemm_slab_kernel, grid, dim3(512), q, false);
   }
   FTMI_CHECK_LAUNCH();
-  if (q.split > 1) {
-    const int64_t total = (int64_t)q.M * q.g[0].N;
-    const int eb = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(eb), dim3(256), 0, s, q);
-    FTMI_CHECK_LAUNCH();
-  }
-  return FTMI_OK;
+  return q.split > 1 ? launch_splitk_finish(q, s) : FTMI_OK;
 }
 
-// skinny kernel eligibility (FTMI_GEMM_SKINNY=0, read per call, turns it off): few rows,
-// same-length output, conv epilogue, groups of equal width, and at most SK_CPB chunks per
-// block for the caller's split (partials in p.part when it splits)
-static bool skinny_ok(const GemmParams &p, int epi) {
-  const char *e = getenv("FTMI_GEMM_SKINNY");
-  if (e && atoi(e) == 0) return false;
+// skinny kernel eligibility: few rows, same-length output, conv epilogue, groups of equal
+// width.  Its blocks take at most SK_CPB chunks each, so it needs skinny_split() splits with
+// partial sums in the caller's workspace, which route() reports.
+static bool skinny_ok(const GemmParams &p, int epi, const Switches &sw) {
+  if (sw.skinny == 0) return false;
   // narrow single-group linears (lin / post_proj at batch 1: N = 80) up to SK_MMAX_NARROW
   // rows: the 128 x 128 tiles would give them a handful of workgroups
   // highway layers up to SK_MMAX_NARROW rows too, always through partial sums (the gating
@@ -4049,23 +3880,34 @@ static bool skinny_ok(const GemmParams &p, int epi) {
   const bool hw = epi == EPI_HIGHWAY;
   const bool narrow = p.ngroups == 1 && (p.g[0].N <= SK_BN * 2 || hw) && p.M <= SK_MMAX_NARROW;
   if ((epi != EPI_CONV && !hw) || p.To != p.T || p.Cin % 16 || p.M <= 0) return false;
-  if (hw && (!p.part || p.ngroups != 1)) return false;
+  if (hw && p.ngroups != 1) return false;
   if (p.M > SK_MMAX && !narrow) return false;
   for (int i = 0; i < p.ngroups; ++i)
     if (p.g[i].k > SL_MAXK || p.g[i].N != p.g[0].N || !p.g[i].w3 || !p.g[i].colscale) return false;
+  return true;
+}
+static int skinny_split(const GemmParams &p, const Switches &sw) {
+  const int nch = (p.Cin + 31) / 32;
+  const int cpb = sw.skinny_cpb < 1 ? 1 : sw.skinny_cpb > SK_CPB ? SK_CPB : (int)sw.skinny_cpb;
+  return (nch + cpb - 1) / cpb;
+}
+// whether the split a caller brought serves the skinny kernel: at most SK_CPB chunks per
+// block, partials in p.part when it splits (a highway layer always: its finish reads them)
+static bool skinny_split_fits(const GemmParams &p, int epi) {
   const int nch = (p.Cin + 31) / 32, S = p.split_req > 1 ? p.split_req : 1;
   const int kc_per = (nch + S - 1) / S;
   if (kc_per > SK_CPB) return false;
-  return (nch + kc_per - 1) / kc_per == 1 || p.part != nullptr;
+  return p.part != nullptr || (epi != EPI_HIGHWAY && (nch + kc_per - 1) / kc_per == 1);
+}
+// a CBHG bank (groups k = K .. 1, even K, 32-column multiples) takes the balanced schedule
+static bool skinny_balanced(const GemmParams &p, int epi, bool maxpool, const Switches &sw) {
+  bool bank = p.ngroups >= 2 && p.ngroups % 2 == 0 && !maxpool && epi == EPI_CONV &&
+              p.g[0].N % 32 == 0 && sw.bank_balanced != 0;
+  for (int i = 0; bank && i < p.ngroups; ++i) bank = p.g[i].k == p.ngroups - i;
+  return bank;
 }
 
-// FTMI_BANK_BALANCED=0 (read per call) keeps a conv bank on the one-group-per-block schedule
-static bool bank_balanced_enabled() {
-  const char *e = getenv("FTMI_BANK_BALANCED");
-  return !(e && atoi(e) == 0);
-}
-
-static int launch_skinny(const GemmParams &p, int epi, bool maxpool, hipStream_t s) {
+static int launch_skinny(const GemmParams &p, int epi, bool maxpool, bool bank, hipStream_t s) {
   GemmParams q = p;
   q.force_part = epi == EPI_HIGHWAY;
   const int nch = (q.Cin + 31) / 32, S = q.split_req > 1 ? q.split_req : 1;
@@ -4077,11 +3919,7 @@ static int launch_skinny(const GemmParams &p, int epi, bool maxpool, hipStream_t
     q.g[i].ntiles = NT;
     q.ldp = max(q.ldp, q.g[i].ycol0 + q.g[i].N);
   }
-  // a CBHG bank (groups k = K .. 1, even K, 16-column multiples): the balanced schedule
-  bool bank = q.ngroups >= 2 && q.ngroups % 2 == 0 && !maxpool && epi == EPI_CONV &&
-              q.g[0].N % 32 == 0 && bank_balanced_enabled();
-  for (int i = 0; bank && i < q.ngroups; ++i) bank = q.g[i].k == q.ngroups - i;
-  if (bank) {
+  if (bank) {  // FTMI_ROUTE_SKINNY_BANK: the balanced schedule
     dim3 grid(MT * (q.ngroups / 2) * (q.g[0].N / 32), q.split), block(512);
 #ifdef FTMI_DIAG
     const char *dg = getenv("FTMI_SKINNY_DIAG");  // timing experiments (results invalid)
@@ -4135,12 +3973,13 @@ static int launch_skinny(const GemmParams &p, int epi, bool maxpool, hipStream_t
 
 // conv_bank_halves_kernel (FTMI_BANK_HALVES): one row tile (M <= 128), groups k = K .. 1 of
 // equal 16-column-multiple widths, Cin a multiple of 64 up to 256, plain conv epilogue into
-// y, the counters + sums workspace; units a multiple of 8 (the block -> (unit, half) map)
+// y; units a multiple of 8 (the block -> (unit, half) map).  Its counters + sums workspace
+// (FTMI_BANK_COUNTERS + bank_halves_floats) comes with the FTMI_BANK_HALVES flag.
 static bool bank_halves_ok(const GemmParams &p) {
   if (p.M <= 0 || p.M > 128 || p.ngroups < 2 || p.ngroups % 2 || p.To != p.T) return false;
   if (p.Cin % 64 || p.Cin > 2 * BH_MAXCH * 32) return false;
   if (!p.y || p.yt || p.residual || p.x_split || p.pool_out || p.y_split_c) return false;
-  if (!p.tile_cnt || !p.part || p.g[0].N % 16) return false;
+  if (p.g[0].N % 16) return false;
   const int units = (p.ngroups / 2) * (p.g[0].N / 16);
   if (units % 8 || units * 8 > FTMI_BANK_COUNTERS) return false;  // 8 counters per unit
   for (int i = 0; i < p.ngroups; ++i)
@@ -4219,11 +4058,10 @@ static int launch_bank_halves(const GemmParams &p, hipStream_t s) {
 // never, 1 at any size.
 constexpr int BW_MIN_BLOCKS = 512;
 int64_t split_block_bytes(int64_t N, int64_t K, int mma);
-static bool bank_walk_ok(const GemmParams &p) {
-  const char *e = getenv("FTMI_BANK_WALK");
-  if (e && atoi(e) == 0) return false;
+static bool bank_walk_ok(const GemmParams &p, const Switches &sw) {
+  if (sw.bank_walk == 0) return false;
   const int64_t blocks = (p.M + SL_BM - 2) / (SL_BM - 1) * ((p.g[0].N + SL_BN - 1) / SL_BN);
-  if (!e && blocks < BW_MIN_BLOCKS) return false;
+  if (sw.bank_walk < 0 && blocks < BW_MIN_BLOCKS) return false;
   if (!p.pool_out || p.x_split || p.residual || p.yt || !p.y || p.split_req > 1) return false;
   if (p.Cin <= 0 || p.Cin > BW_MAXCH * 32 || p.Cin % 16 || p.To != p.T || p.M <= 0) return false;
   if (p.T < 4 || p.ngroups < 2 || p.ngroups > BW_MAXK || p.g[0].N % SL_BN) return false;
@@ -4260,109 +4098,116 @@ static int launch_bank_walk(const GemmParams &p, hipStream_t s) {
   return FTMI_OK;
 }
 
+// The one decision function: which kernel a launch takes.  Pure host code.  A split the
+// caller chose (p.split_req, p.part) only matters where a slab kernel has to accept it; the
+// splits the skinny and halves kernels need are reported, not read.
+static Route route(const GemmParams &p, int epi, bool maxpool, int mma, const Switches &sw) {
+  Route r = {FTMI_ROUTE_UNSUPPORTED, 0, 0, false, false, 0};
+  bool presplit = mma != 0;
+  for (int i = 0; i < p.ngroups; ++i) presplit &= p.g[i].w3 != nullptr;
+  const bool f16 = mma == 2 && presplit;
+  if (mma == 2 && !f16) return r;  // the f16 path needs the split planes
+  if (p.pool_out) {  // only the slab kernels pool their output, and they do not split then
+    GemmParams q = p;
+    q.split_req = 0;
+    q.part = nullptr;
+    if (!(f16 && epi == EPI_CONV && !maxpool && !p.residual && !p.yt && p.y && slab_ok(q, epi, sw)))
+      return r;
+    r.pooled = r.drop_split = true;
+    if (bank_walk_ok(q, sw))
+      r.kernel = FTMI_ROUTE_BANK_WALK;
+    else
+      take_slab(r, q, false, sw);
+    return r;
+  }
+  if (p.y_split_c) return r;  // split output rows: pool_out only
+  if (p.x_split) {  // split operand rows: only the slab kernels stage them
+    if (f16 && !maxpool && slab_ok(p, epi, sw)) take_slab(r, p, false, sw);
+    return r;
+  }
+  if (f16 && epi == EPI_CONV && !maxpool && sw.bank_halves != 0 && bank_halves_ok(p)) {
+    r.kernel = FTMI_ROUTE_BANK_HALVES;
+    r.split = 2;
+    r.ws_floats = FTMI_BANK_COUNTERS + bank_halves_floats(p.M, p.ngroups, p.g[0].N);
+    return r;
+  }
+  if (f16 && skinny_ok(p, epi, sw)) {
+    r.kernel = skinny_balanced(p, epi, maxpool, sw) ? FTMI_ROUTE_SKINNY_BANK : FTMI_ROUTE_SKINNY;
+    const int S = skinny_split(p, sw);
+    if (S > 1 || epi == EPI_HIGHWAY) {  // partial sums of every group's columns
+      int ldp = 0;
+      for (int i = 0; i < p.ngroups; ++i) ldp = max(ldp, p.g[i].ycol0 + p.g[i].N);
+      r.split = S;
+      r.ws_floats = (int64_t)S * p.M * ldp;
+    }
+    return r;
+  }
+  // a bank's or a highway layer's split only serves the skinny kernel
+  r.drop_split = p.ngroups > 1 || epi == EPI_HIGHWAY;
+  GemmParams q = p;
+  if (r.drop_split) {
+    q.split_req = 0;
+    q.part = nullptr;
+  }
+  if (f16 && slab_ok(q, epi, sw))
+    take_slab(r, q, maxpool, sw);
+  else if (presplit)
+    r.kernel = f16 ? FTMI_ROUTE_X6B_F16 : FTMI_ROUTE_X6B_BF16;
+  else
+    r.kernel = mma == 1 ? FTMI_ROUTE_X6 : FTMI_ROUTE_F32;
+  return r;
+}
+
 int launch(const GemmParams &p, int epi, bool maxpool, int nblocks, int mma, hipStream_t s) {
   if (nblocks <= 0) return FTMI_OK;
-  dim3 grid(nblocks), block(256);
-  bool presplit = (mma == 1 && x6_variant() != 3) || mma == 2;
-  for (int i = 0; i < p.ngroups; ++i) presplit &= p.g[i].w3 != nullptr;
-  if (mma == 2 && !presplit) return FTMI_E_ARG;  // the f16 path needs the split planes
-  if (p.pool_out) {  // only the slab kernel pools its output
-    GemmParams q = p;
+  for (int i = 0; mma == 2 && i < p.ngroups; ++i)
+    if (!p.g[i].w3) return FTMI_E_ARG;  // the f16 path needs the split planes
+  Switches sw = read_switches();
+  sw.bank_halves = 0;  // the one-launch bank comes with its flag and workspace, never from here
+  Route r = route(p, epi, maxpool, mma, sw);
+  const auto skinny = [&] { return r.kernel == FTMI_ROUTE_SKINNY || r.kernel == FTMI_ROUTE_SKINNY_BANK; };
+  if (skinny() && !skinny_split_fits(p, epi)) {
+    // a caller that did not bring the skinny kernel's split is routed without that kernel
+    sw.skinny = 0;
+    r = route(p, epi, maxpool, mma, sw);
+  }
+  GemmParams q = p;
+  if (r.drop_split) {
     q.split_req = 0;
     q.part = nullptr;
-    if (!(mma == 2 && presplit && epi == EPI_CONV && !maxpool && !p.residual && !p.yt &&
-          p.y && slab_ok(q, epi)))
+  }
+  switch (r.kernel) {
+    case FTMI_ROUTE_UNSUPPORTED:
       return FTMI_E_UNSUPPORTED;
-    if (bank_walk_ok(q)) return launch_bank_walk(q, s);
-    return launch_slab(q, epi, false, s);
+    case FTMI_ROUTE_SKINNY:
+    case FTMI_ROUTE_SKINNY_BANK:
+      return launch_skinny(q, epi, maxpool, r.kernel == FTMI_ROUTE_SKINNY_BANK, s);
+    case FTMI_ROUTE_SLAB:
+    case FTMI_ROUTE_SLAB_WS:
+    case FTMI_ROUTE_SLAB_PF:
+      return launch_slab(q, epi, maxpool, r, s);
+    case FTMI_ROUTE_BANK_WALK:
+      return launch_bank_walk(q, s);
+    default:
+      break;
   }
-  if (p.y_split_c) return FTMI_E_UNSUPPORTED;  // split output rows: pool_out only
-  if (p.x_split) {  // split operand rows: only the slab kernel stages them
-    if (!(mma == 2 && presplit && !maxpool && slab_ok(p, epi))) return FTMI_E_UNSUPPORTED;
-    return launch_slab(p, epi, false, s);
+  // the 128 x 128 tile kernels: splits in blockIdx.y
+  const dim3 grid(nblocks, q.split > 1 && mma != 0 ? q.split : 1), block(256);
+  switch (r.kernel) {
+    case FTMI_ROUTE_X6B_F16:
+      FTMI_LAUNCH_EPI(conv_gemm_x6b_kernel, grid, block, q, true);
+      break;
+    case FTMI_ROUTE_X6B_BF16:
+      FTMI_LAUNCH_EPI(conv_gemm_x6b_kernel, grid, block, q, false);
+      break;
+    case FTMI_ROUTE_X6:
+      FTMI_LAUNCH_EPI(conv_gemm_x6_kernel, grid, block, q);
+      break;
+    default:
+      FTMI_LAUNCH_EPI(conv_gemm_kernel, grid, block, q);
   }
-  if (mma == 2 && presplit && skinny_ok(p, epi)) return launch_skinny(p, epi, maxpool, s);
-  if (p.ngroups > 1 && p.split_req > 1) {  // a bank split only serves the skinny kernel
-    GemmParams q = p;
-    q.split_req = 0;
-    q.part = nullptr;
-    return launch(q, epi, maxpool, nblocks, mma, s);
-  }
-  if (mma == 2 && slab_ok(p, epi)) return launch_slab(p, epi, maxpool, s);
-  if (presplit) {
-    dim3 g2(nblocks, p.split > 1 ? p.split : 1);
-    if (mma == 2) {
-      if (epi == EPI_HIGHWAY)
-        hipLaunchKernelGGL((conv_gemm_x6b_kernel<EPI_HIGHWAY, false, true>), g2, block, 0, s, p);
-      else if (maxpool)
-        hipLaunchKernelGGL((conv_gemm_x6b_kernel<EPI_CONV, true, true>), g2, block, 0, s, p);
-      else
-        hipLaunchKernelGGL((conv_gemm_x6b_kernel<EPI_CONV, false, true>), g2, block, 0, s, p);
-    } else {
-      if (epi == EPI_HIGHWAY)
-        hipLaunchKernelGGL((conv_gemm_x6b_kernel<EPI_HIGHWAY, false, false>), g2, block, 0, s, p);
-      else if (maxpool)
-        hipLaunchKernelGGL((conv_gemm_x6b_kernel<EPI_CONV, true, false>), g2, block, 0, s, p);
-      else
-        hipLaunchKernelGGL((conv_gemm_x6b_kernel<EPI_CONV, false, false>), g2, block, 0, s, p);
-    }
-    FTMI_CHECK_LAUNCH();
-    if (p.split > 1) {
-      const int64_t total = (int64_t)p.M * p.g[0].N;
-      const int eb = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(eb), block, 0, s, p);
-      FTMI_CHECK_LAUNCH();
-    }
-    return FTMI_OK;
-  }
-  if (mma == 1 && x6_variant() == 2) {  // software-pipelined variant
-    dim3 g2(nblocks, p.split > 1 ? p.split : 1);
-    if (epi == EPI_HIGHWAY)
-      hipLaunchKernelGGL((conv_gemm_x6p_kernel<EPI_HIGHWAY, false>), g2, block, 0, s, p);
-    else if (maxpool)
-      hipLaunchKernelGGL((conv_gemm_x6p_kernel<EPI_CONV, true>), g2, block, 0, s, p);
-    else
-      hipLaunchKernelGGL((conv_gemm_x6p_kernel<EPI_CONV, false>), g2, block, 0, s, p);
-    FTMI_CHECK_LAUNCH();
-    if (p.split > 1) {
-      const int64_t total = (int64_t)p.M * p.g[0].N;
-      const int eb = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(eb), block, 0, s, p);
-      FTMI_CHECK_LAUNCH();
-    }
-    return FTMI_OK;
-  }
-  if (mma == 1 && p.split > 1) {
-    dim3 g2(nblocks, p.split);
-    if (maxpool)
-      hipLaunchKernelGGL((conv_gemm_x6_kernel<EPI_CONV, true>), g2, block, 0, s, p);
-    else
-      hipLaunchKernelGGL((conv_gemm_x6_kernel<EPI_CONV, false>), g2, block, 0, s, p);
-    FTMI_CHECK_LAUNCH();
-    const int64_t total = (int64_t)p.M * p.g[0].N;
-    const int eb = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(eb), block, 0, s, p);
-    FTMI_CHECK_LAUNCH();
-    return FTMI_OK;
-  }
-  if (mma == 1) {
-    if (epi == EPI_HIGHWAY)
-      hipLaunchKernelGGL((conv_gemm_x6_kernel<EPI_HIGHWAY, false>), grid, block, 0, s, p);
-    else if (maxpool)
-      hipLaunchKernelGGL((conv_gemm_x6_kernel<EPI_CONV, true>), grid, block, 0, s, p);
-    else
-      hipLaunchKernelGGL((conv_gemm_x6_kernel<EPI_CONV, false>), grid, block, 0, s, p);
-    FTMI_CHECK_LAUNCH();
-    return FTMI_OK;
-  }
-  if (epi == EPI_HIGHWAY)
-    hipLaunchKernelGGL((conv_gemm_kernel<EPI_HIGHWAY, false>), grid, block, 0, s, p);
-  else if (maxpool)
-    hipLaunchKernelGGL((conv_gemm_kernel<EPI_CONV, true>), grid, block, 0, s, p);
-  else
-    hipLaunchKernelGGL((conv_gemm_kernel<EPI_CONV, false>), grid, block, 0, s, p);
   FTMI_CHECK_LAUNCH();
-  return FTMI_OK;
+  return grid.y > 1 ? launch_splitk_finish(q, s) : FTMI_OK;
 }
 
 // bytes of one weight's pre-split block: bf16 pieces (mma = 1) or f16 planes + colscale
@@ -4377,9 +4222,12 @@ void set_split(GemmGroup &g, const void *block, int mma) {
                                    : nullptr;
 }
 
-}  // namespace
+void export_route(const Route &r, ftmi_gemm_route *out) {
+  *out = {r.kernel, r.split, r.ws_floats, r.pooled ? 1 : 0, r.band};
+}
 
-extern "C" int ftmi_conv1d(const ftmi_conv_args *a, ftmi_stream_t stream) {
+// ftmi_conv1d's argument checks and GemmParams, shared with ftmi_conv1d_route
+int conv_params(const ftmi_conv_args *a, GemmParams &p) {
   if (!a || !a->x || !a->w || (!a->y && !a->yt)) return FTMI_E_ARG;
   if (a->B <= 0 || a->T <= 0 || a->Cin <= 0 || a->N <= 0 || a->k <= 0) return FTMI_E_ARG;
   if (a->Cin % 16 != 0) return FTMI_E_SHAPE;
@@ -4391,7 +4239,7 @@ extern "C" int ftmi_conv1d(const ftmi_conv_args *a, ftmi_stream_t stream) {
   if (a->w_split && !ftmi_aligned16(a->w_split)) return FTMI_E_ALIGN;
   const int To = a->T_out > 0 ? a->T_out : a->T;
   if ((int64_t)a->B * To > INT32_MAX) return FTMI_E_SHAPE;
-  GemmParams p = {};
+  p = {};
   p.x = a->x;
   p.x_stride = a->x_stride;
   p.B = a->B;
@@ -4425,7 +4273,6 @@ extern "C" int ftmi_conv1d(const ftmi_conv_args *a, ftmi_stream_t stream) {
   g.ntiles = (a->N + BN - 1) / BN;
   g.tile0 = 0;
   set_split(g, a->w_split, a->mma);
-  const int mtiles = (p.M + BM - 1) / BM;
   p.split = 1;
   if (a->split_k > 1) {
     if (a->mma == 0 || !a->split_ws) return FTMI_E_ARG;
@@ -4436,7 +4283,29 @@ extern "C" int ftmi_conv1d(const ftmi_conv_args *a, ftmi_stream_t stream) {
     p.split_req = a->split_k;
     p.part = a->split_ws;
   }
-  return launch(p, EPI_CONV, a->maxpool != 0, mtiles * g.ntiles, a->mma, ftmi_hs(stream));
+  return FTMI_OK;
+}
+
+}  // namespace
+
+extern "C" uint64_t ftmi_gemm_switches_digest(void) { return read_switches().digest; }
+
+extern "C" int ftmi_conv1d(const ftmi_conv_args *a, ftmi_stream_t stream) {
+  GemmParams p;
+  if (const int rc = conv_params(a, p)) return rc;
+  const int tiles = (p.M + BM - 1) / BM * p.g[0].ntiles;
+  return launch(p, EPI_CONV, a->maxpool != 0, tiles, a->mma, ftmi_hs(stream));
+}
+
+extern "C" int ftmi_conv1d_route(const ftmi_conv_args *a, ftmi_gemm_route *out) {
+  if (!a || !out) return FTMI_E_ARG;
+  ftmi_conv_args b = *a;  // the split is the answer, not a question
+  b.split_k = 0;
+  b.split_ws = nullptr;
+  GemmParams p;
+  if (const int rc = conv_params(&b, p)) return rc;
+  export_route(route(p, EPI_CONV, b.maxpool != 0, b.mma, read_switches()), out);
+  return FTMI_OK;
 }
 
 namespace {
@@ -4542,12 +4411,13 @@ extern "C" int ftmi_debug_skinny_stamps(unsigned long long *host, int n) {
 }
 #endif
 
-extern "C" int ftmi_conv_bank_split(const float *x, int64_t x_stride, int32_t B, int32_t T,
-                                    int32_t Cin, const float *w, const void *w_split, int32_t K,
-                                    int32_t Cout, const float *bn_scale, const float *bn_shift,
-                                    float *y, int64_t y_stride, int32_t mma, uint32_t *status,
-                                    int32_t split_k, float *split_ws, int32_t pool_out,
-                                    ftmi_stream_t stream) {
+// ftmi_conv_bank_split's argument checks and GemmParams, shared with ftmi_conv_bank_route;
+// *tiles: the tile count of the generic kernels
+static int bank_params(const float *x, int64_t x_stride, int32_t B, int32_t T, int32_t Cin,
+                       const float *w, const void *w_split, int32_t K, int32_t Cout,
+                       const float *bn_scale, const float *bn_shift, float *y, int64_t y_stride,
+                       int32_t mma, uint32_t *status, int32_t split_k, float *split_ws,
+                       int32_t pool_out, GemmParams &p, int *tiles) {
   if (split_k > 1 && !split_ws && !(pool_out & FTMI_BANK_POOL)) return FTMI_E_ARG;
   if (!x || !w || !bn_scale || !bn_shift || !y) return FTMI_E_ARG;
   if (B <= 0 || T <= 0 || Cin <= 0 || Cout <= 0 || K <= 0) return FTMI_E_ARG;
@@ -4557,7 +4427,7 @@ extern "C" int ftmi_conv_bank_split(const float *x, int64_t x_stride, int32_t B,
   if (!ftmi_aligned16(x) || !ftmi_aligned16(w) || (x_stride & 3)) return FTMI_E_ALIGN;
   if (w_split && !ftmi_aligned16(w_split)) return FTMI_E_ALIGN;
   if ((int64_t)B * T > INT32_MAX) return FTMI_E_SHAPE;
-  GemmParams p = {};
+  p = {};
   p.x = x;
   p.x_stride = x_stride;
   p.B = B;
@@ -4586,8 +4456,7 @@ extern "C" int ftmi_conv_bank_split(const float *x, int64_t x_stride, int32_t B,
   }
   p.x_split = (pool_out & FTMI_BANK_X_SPLIT) != 0;
   if (p.x_split && mma != 2) return FTMI_E_UNSUPPORTED;
-  const int tile0 = set_bank_groups(p, w, image ? nullptr : w_split, K, Cout, mma, bn_scale,
-                                    bn_shift);
+  *tiles = set_bank_groups(p, w, image ? nullptr : w_split, K, Cout, mma, bn_scale, bn_shift);
   if (halves) {  // one launch: channel halves, the unit's last half finishes it
     p.tile_cnt = (unsigned *)split_ws;
     p.part = split_ws + FTMI_BANK_COUNTERS;
@@ -4601,14 +4470,43 @@ extern "C" int ftmi_conv_bank_split(const float *x, int64_t x_stride, int32_t B,
         p.g[gi].colscale = cs + (int64_t)(K - 1 - gi) * Cout;
       }
     }
-    if (!bank_halves_ok(p)) return FTMI_E_UNSUPPORTED;
-    return launch_bank_halves(p, ftmi_hs(stream));
+    return bank_halves_ok(p) ? FTMI_OK : FTMI_E_UNSUPPORTED;
   }
   if (split_k > 1) {
     p.split_req = split_k;
     p.part = split_ws;
   }
-  return launch(p, EPI_CONV, false, tile0, mma, ftmi_hs(stream));
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_conv_bank_split(const float *x, int64_t x_stride, int32_t B, int32_t T,
+                                    int32_t Cin, const float *w, const void *w_split, int32_t K,
+                                    int32_t Cout, const float *bn_scale, const float *bn_shift,
+                                    float *y, int64_t y_stride, int32_t mma, uint32_t *status,
+                                    int32_t split_k, float *split_ws, int32_t pool_out,
+                                    ftmi_stream_t stream) {
+  GemmParams p;
+  int tiles = 0;
+  if (const int rc = bank_params(x, x_stride, B, T, Cin, w, w_split, K, Cout, bn_scale, bn_shift, y,
+                                 y_stride, mma, status, split_k, split_ws, pool_out, p, &tiles))
+    return rc;
+  if (pool_out & FTMI_BANK_HALVES) return launch_bank_halves(p, ftmi_hs(stream));
+  return launch(p, EPI_CONV, false, tiles, mma, ftmi_hs(stream));
+}
+
+extern "C" int ftmi_conv_bank_route(const float *x, int64_t x_stride, int32_t B, int32_t T,
+                                    int32_t Cin, const float *w, const void *w_split, int32_t K,
+                                    int32_t Cout, const float *bn_scale, const float *bn_shift,
+                                    float *y, int64_t y_stride, int32_t mma, uint32_t *status,
+                                    int32_t flags, ftmi_gemm_route *out) {
+  if (!out || (flags & ~(FTMI_BANK_POOL | FTMI_BANK_Y_SPLIT | FTMI_BANK_X_SPLIT))) return FTMI_E_ARG;
+  GemmParams p;
+  int tiles = 0;
+  if (const int rc = bank_params(x, x_stride, B, T, Cin, w, w_split, K, Cout, bn_scale, bn_shift, y,
+                                 y_stride, mma, status, 0, nullptr, flags, p, &tiles))
+    return rc;
+  export_route(route(p, EPI_CONV, false, mma, read_switches()), out);
+  return FTMI_OK;
 }
 
 extern "C" int ftmi_highway(const float *x, int64_t x_stride, int64_t M, int32_t C,
@@ -4619,11 +4517,11 @@ extern "C" int ftmi_highway(const float *x, int64_t x_stride, int64_t M, int32_t
                             status, 0, nullptr, stream);
 }
 
-extern "C" int ftmi_highway_split(const float *x, int64_t x_stride, int64_t M, int32_t C,
-                                  const float *w12, const void *w12_split, const float *b1,
-                                  const float *b2, float *y, int64_t y_stride, int32_t mma,
-                                  uint32_t *status, int32_t split_k, float *split_ws,
-                                  ftmi_stream_t stream) {
+// ftmi_highway_split's argument checks and GemmParams, shared with ftmi_highway_route
+static int highway_params(const float *x, int64_t x_stride, int64_t M, int32_t C, const float *w12,
+                          const void *w12_split, const float *b1, const float *b2, float *y,
+                          int64_t y_stride, int32_t mma, uint32_t *status, int32_t split_k,
+                          float *split_ws, GemmParams &p) {
   if (!x || !w12 || !b1 || !b2 || !y) return FTMI_E_ARG;
   if (split_k >= 1 && !split_ws) return FTMI_E_ARG;
   if (M <= 0 || C <= 0) return FTMI_E_ARG;
@@ -4633,7 +4531,7 @@ extern "C" int ftmi_highway_split(const float *x, int64_t x_stride, int64_t M, i
   if (!ftmi_aligned16(x) || !ftmi_aligned16(w12) || (x_stride & 3)) return FTMI_E_ALIGN;
   if (w12_split && !ftmi_aligned16(w12_split)) return FTMI_E_ALIGN;
   if (x == y) return FTMI_E_ARG;
-  GemmParams p = {};
+  p = {};
   p.x = x;
   p.x_stride = x_stride;
   p.B = 1;
@@ -4657,14 +4555,37 @@ extern "C" int ftmi_highway_split(const float *x, int64_t x_stride, int64_t M, i
   g.ntiles = (2 * C + BN - 1) / BN;
   g.tile0 = 0;
   set_split(g, w12_split, mma);
-  const int mtiles = (p.M + BM - 1) / BM;
-  if (split_k >= 1 && mma == 2 && w12_split) {  // skinny kernel: partial sums + highway finish
-    GemmParams q = p;
-    q.split_req = split_k;
-    q.part = split_ws;
-    if (skinny_ok(q, EPI_HIGHWAY)) return launch_skinny(q, EPI_HIGHWAY, false, ftmi_hs(stream));
+  if (split_k >= 1) {  // skinny kernel: partial sums + highway finish; other kernels drop it
+    p.split_req = split_k;
+    p.part = split_ws;
   }
-  return launch(p, EPI_HIGHWAY, false, mtiles * g.ntiles, mma, ftmi_hs(stream));
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_highway_split(const float *x, int64_t x_stride, int64_t M, int32_t C,
+                                  const float *w12, const void *w12_split, const float *b1,
+                                  const float *b2, float *y, int64_t y_stride, int32_t mma,
+                                  uint32_t *status, int32_t split_k, float *split_ws,
+                                  ftmi_stream_t stream) {
+  GemmParams p;
+  if (const int rc = highway_params(x, x_stride, M, C, w12, w12_split, b1, b2, y, y_stride, mma,
+                                    status, split_k, split_ws, p))
+    return rc;
+  const int tiles = (p.M + BM - 1) / BM * p.g[0].ntiles;
+  return launch(p, EPI_HIGHWAY, false, tiles, mma, ftmi_hs(stream));
+}
+
+extern "C" int ftmi_highway_route(const float *x, int64_t x_stride, int64_t M, int32_t C,
+                                  const float *w12, const void *w12_split, const float *b1,
+                                  const float *b2, float *y, int64_t y_stride, int32_t mma,
+                                  uint32_t *status, ftmi_gemm_route *out) {
+  if (!out) return FTMI_E_ARG;
+  GemmParams p;
+  if (const int rc = highway_params(x, x_stride, M, C, w12, w12_split, b1, b2, y, y_stride, mma,
+                                    status, 0, nullptr, p))
+    return rc;
+  export_route(route(p, EPI_HIGHWAY, false, mma, read_switches()), out);
+  return FTMI_OK;
 }
 
 // f16 planes + column scales of a split_weights_f16 block [3][N][Kpad] + colscale[N]

@@ -150,36 +150,15 @@ def _num_cus() -> int:
     return n
 
 
-SLAB = os.environ.get('FTMI_GEMM_SLAB', '1') != '0'
-
-
-SLAB_K1_NMIN = int(os.environ.get('FTMI_SLAB_K1_NMIN', 128))  # gemm.hip slab_ok
-
-
-def _slab(mma: int, T: int, To: int, Cin: int, k: int, N: int, M: int) -> bool:
-    """Whether ftmi_conv1d takes the slab kernel (gemm.hip slab_ok)."""
-    return (SLAB and mma == 2 and To == T and Cin % 16 == 0 and k <= 16 and (k > 1 or N >= SLAB_K1_NMIN)
-            and M * N * k * Cin >= int(os.environ.get('FTMI_GEMM_SLAB_MIN', 0)))
-
-
-SKINNY_MMAX = 256          # gemm.hip SK_MMAX
-SKINNY_MMAX_NARROW = 1024  # gemm.hip SK_MMAX_NARROW (single group, N <= 128)
-
-
-def _skinny(mma: int, T: int, To: int, Cin: int, k: int, M: int, N: Optional[int] = None) -> bool:
-    """Whether a conv takes the weight-streaming skinny kernel (gemm.hip skinny_ok): few
-    rows (B = 1 generation) — or a narrow single-group linear (N <= 128) with up to 1024
-    rows — f16x3, same-length output.  N = None: a multi-group call (conv bank)."""
-    rows_ok = 0 < M <= SKINNY_MMAX or (N is not None and N <= 128 and 0 < M <= SKINNY_MMAX_NARROW)
-    return (os.environ.get('FTMI_GEMM_SKINNY', '1') != '0' and mma == 2 and To == T
-            and Cin % 16 == 0 and k <= 16 and rows_ok)
-
-
-def _skinny_split(Cin: int) -> int:
-    """Channel split of the skinny kernel: two 32-channel chunks per block."""
-    nch = -(-Cin // 32)
-    per = int(os.environ.get('FTMI_SKINNY_CPB', 2))  # chunks per block (1 or 2; A/B runs)
-    return -(-nch // per)
+def _route(query: str, *args) -> _lib.GemmRoute:
+    """The kernel the library will take for the launch these arguments describe, with the
+    split and workspace floats that kernel requires (include/ftmi.h ftmi_*_route: the
+    library's one decision function, host only).  Arguments the entry point refuses give an
+    empty route: the launch that follows reports them."""
+    r = _lib.GemmRoute()
+    if getattr(_lib.load(), query)(*args, ctypes.byref(r)) != 0:
+        return _lib.GemmRoute()
+    return r
 
 
 def _split_k(M: int, N: int, K: int, mma: int, slab: bool = False, Cin: int = 0) -> int:
@@ -368,12 +347,14 @@ def conv1d(x: torch.Tensor, w: torch.Tensor, k: int, pad: int, *, bias=None, rel
     a.status = status_word(x.device).data_ptr()
     a.x_split = int(x_split)
     M = B * To
-    if _skinny(a.mma, T, To, Cin, k, M, N):
-        sk = _skinny_split(Cin)
+    r = _route('ftmi_conv1d_route', ctypes.byref(a))
+    if r.kernel in _lib.ROUTE_SKINNIES:  # the split is the kernel's, not a tuning choice
+        sk, ws = r.split_k, r.ws_floats
     else:
-        sk = _split_k(M, N, k * Cin, a.mma, _slab(a.mma, T, To, Cin, k, N, M), Cin)
+        sk = _split_k(M, N, k * Cin, a.mma, r.kernel in _lib.ROUTE_SLABS, Cin)
+        ws = sk * M * N
     if sk > 1:
-        part = _new(sk * M * N, device=x.device)
+        part = _new(ws, device=x.device)
         a.split_k, a.split_ws = sk, part.data_ptr()
     label = (f'conv1d[M={M},N={N},K={k * Cin}{",maxpool" if maxpool else ""}'
              f'{",xsplit" if x_split else ""},mma={a.mma}]')
@@ -394,12 +375,17 @@ SPLIT_BANK_IN = os.environ.get('FTMI_SPLIT_BANK_IN', '0') == '1'
 
 
 def bank_pools(x: torch.Tensor, K: int, Cout: int, mma: Optional[int] = None, w_split=None) -> bool:
-    """Whether conv_bank(pool=True) applies (gemm.hip launch: the f16x3 slab kernel, not the
-    few-row skinny kernel): then the bank stores the CBHG maxpool of its output itself."""
+    """Whether conv_bank(pool=True) applies: the library routes the pooled bank of x (its
+    address and row stride; the output and the BN vectors as conv_bank allocates them,
+    16-byte aligned and dense) to a kernel that stores the CBHG maxpool itself, where the
+    few-row bank takes the skinny or halves kernel instead."""
+    if not POOL_BANK:
+        return False
     m, wsp = _gemm_mma(mma, w_split)
     B, T, Cin = x.size(0), x.size(1), x.size(2)
-    return (POOL_BANK and m == 2 and wsp is not None and not _skinny(m, T, T, Cin, K, B * T)
-            and _slab(m, T, T, Cin, K, Cout, B * T))
+    at = dict(x=x.data_ptr(), xs=x.stride(-2), wsp=wsp)
+    return (_bank_route(m, B, T, Cin, K, Cout, **at).kernel in _lib.ROUTE_SLABS
+            and bool(_bank_route(m, B, T, Cin, K, Cout, flags=BANK_POOL, **at).pooled))
 
 
 def bank_halves_image(w_split: Optional[torch.Tensor], K: int, Cin: int,
@@ -440,41 +426,49 @@ def conv_bank(x: torch.Tensor, w: torch.Tensor, K: int, Cout: int, scale: torch.
     M = B * T
     flops = 2.0 * M * Cout * Cin * K * (K + 1) / 2
     mma, wsp = _gemm_mma(mma, w_split)
-    sk, part, last = 0, None, 0
-    if not pool and not x_split and _bank_halves(mma, B, T, Cin, K, Cout):
+    flags = int(pool) | (BANK_Y_SPLIT * int(split_out)) | (BANK_X_SPLIT * int(x_split))
+    r = _bank_route(mma, B, T, Cin, K, Cout, x=x.data_ptr(), xs=xs, w=w.data_ptr(), wsp=wsp,
+                    scale=scale.data_ptr(), shift=shift.data_ptr(), y=y.data_ptr(),
+                    ys=y.stride(-2), flags=flags)
+    sk, part = r.split_k, None
+    if r.kernel == _lib.ROUTE_BANK_HALVES:
         # the few-row bank in one launch (gemm.hip conv_bank_halves_kernel)
-        n = int(_lib.load().ftmi_conv_bank_halves_ws_floats(B, T, K, Cout)) - BANK_COUNTERS
-        sk, part, last = 2, _bank_workspace(n, x.device), BANK_HALVES
+        part, flags = _bank_workspace(r.ws_floats - BANK_COUNTERS, x.device), BANK_HALVES
         if w_image is not None:
             _dev(w_image)
-            wsp, last = w_image.data_ptr(), BANK_HALVES | BANK_IMAGE
-    elif not pool and _skinny(mma, T, T, Cin, K, M) and _skinny_split(Cin) > 1:
-        sk = _skinny_split(Cin)  # weight-streaming kernel: partial sums, finished in order
-        part = torch.empty(sk * M * K * Cout, device=x.device, dtype=_f32)
+            wsp, flags = w_image.data_ptr(), BANK_HALVES | BANK_IMAGE
+    elif sk > 1:  # weight-streaming kernel: partial sums, finished in order
+        part = torch.empty(r.ws_floats, device=x.device, dtype=_f32)
     launch('ftmi_conv_bank_split', f'conv_bank[M={M},K={K},Cin={Cin},mma={mma}'
            f'{",pool" if pool else ""}{",split" if split_out else ""}{",xsplit" if x_split else ""}'
            ']',
            flops, 4.0 * (M * Cin + Cout * Cin * K * (K + 1) / 2 + M * K * Cout),
            x.data_ptr(), xs, B, T, Cin, w.data_ptr(), wsp, K, Cout,
            scale.data_ptr(), shift.data_ptr(), y.data_ptr(), y.stride(-2), mma,
-           status_word(x.device).data_ptr(), sk, _ptr(part),
-           int(pool) | (2 * int(split_out)) | (4 * int(x_split)) | last, _stream())
+           status_word(x.device).data_ptr(), sk, _ptr(part), flags, _stream())
     return y
 
 
 BANK_COUNTERS = 4096  # include/ftmi.h FTMI_BANK_COUNTERS
-BANK_HALVES, BANK_IMAGE = 16, 32  # include/ftmi.h FTMI_BANK_HALVES / _IMAGE
+# include/ftmi.h FTMI_BANK_*
+BANK_POOL, BANK_Y_SPLIT, BANK_X_SPLIT, BANK_HALVES, BANK_IMAGE = 1, 2, 4, 16, 32
+_FAKE = 1 << 12  # a 16-byte aligned stand-in for an address a route query never reads
+
+
+def _bank_route(mma: int, B: int, T: int, Cin: int, K: int, Cout: int, *, x=_FAKE, xs=None,
+                w=_FAKE, wsp=_FAKE, scale=_FAKE, shift=_FAKE, y=_FAKE, ys=None,
+                flags: int = 0) -> _lib.GemmRoute:
+    """ftmi_conv_bank_route of a bank; operands not given count as dense and aligned."""
+    return _route('ftmi_conv_bank_route', x, Cin if xs is None else xs, B, T, Cin, w, wsp, K, Cout,
+                  scale, shift, y, K * Cout if ys is None else ys, mma, None, flags)
 
 
 def _bank_halves(mma: int, B: int, T: int, Cin: int, K: int, Cout: int) -> bool:
-    """Whether conv_bank takes the one-launch channel-halves kernel (gemm.hip
-    bank_halves_ok): f16x3, one row tile of at most 128 rows (batch-1 generation, BASELINE
-    config c2), Cin a multiple of 64 up to 256, even K, (K / 2)(Cout / 16) a multiple of 8 up
-    to 512 (8 arrival counters per unit).
-    FTMI_BANK_HALVES=0 (read per call) keeps the channel-split kernel + finish."""
-    return (os.environ.get('FTMI_BANK_HALVES', '1') != '0' and mma == 2 and 0 < B * T <= 128
-            and Cin % 64 == 0 and Cin <= 256 and K % 2 == 0 and Cout % 16 == 0
-            and (K // 2) * (Cout // 16) % 8 == 0 and (K // 2) * (Cout // 16) <= 512 and K <= 16)
+    """Whether conv_bank takes the one-launch channel-halves kernel (FTMI_ROUTE_BANK_HALVES:
+    batch-1 generation, BASELINE config c2) for a dense, aligned bank of this shape."""
+    return _bank_route(mma, B, T, Cin, K, Cout).kernel == _lib.ROUTE_BANK_HALVES
+
+
 _BANK_WS = {}
 
 
@@ -581,16 +575,14 @@ def highway(x: torch.Tensor, w12: torch.Tensor, b1: torch.Tensor, b2: torch.Tens
     y = out if out is not None else torch.empty(B, T, C, device=x.device, dtype=_f32)
     M = B * T
     mma, wsp = _gemm_mma(mma, w_split)
-    sk, part = 0, None
-    if (mma == 2 and wsp is not None and os.environ.get('FTMI_GEMM_SKINNY', '1') != '0'
-            and C % 16 == 0 and 0 < M <= SKINNY_MMAX_NARROW):
-        sk = _skinny_split(C)  # weight-streaming kernel: partials + the highway finish
-        part = torch.empty(sk * M * 2 * C, device=x.device, dtype=_f32)
+    at = (x.data_ptr(), xs, M, C, w12.data_ptr(), wsp, b1.data_ptr(), b2.data_ptr(), y.data_ptr(),
+          y.stride(1), mma, status_word(x.device).data_ptr())
+    r = _route('ftmi_highway_route', *at)
+    sk, part = r.split_k, None
+    if sk:  # weight-streaming kernel: partials + the highway finish
+        part = torch.empty(r.ws_floats, device=x.device, dtype=_f32)
     launch('ftmi_highway_split', f'highway[M={M},C={C},mma={mma}]', 2.0 * M * 2 * C * C,
-           4.0 * (2 * M * C + 2 * C * C),
-           x.data_ptr(), xs, M, C, w12.data_ptr(), wsp, b1.data_ptr(),
-           b2.data_ptr(), y.data_ptr(), y.stride(1), mma, status_word(x.device).data_ptr(),
-           sk, _ptr(part), _stream())
+           4.0 * (2 * M * C + 2 * C * C), *at, sk, _ptr(part), _stream())
     return y
 
 

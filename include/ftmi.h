@@ -88,7 +88,9 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * added under 20 without a signature change: ftmi_align_workspace_bytes,
  * ftmi_align_dijkstra, ftmi_align_count, ftmi_attention_score; ftmi_phoneme_features,
  * ftmi_nonzero_moments, ftmi_normalize_nonzero; ftmi_embed_bank; ftmi_l1_loss,
- * ftmi_cross_entropy, ftmi_mol_loss and their *_workspace_bytes; ftmi_run_chain). */
+ * ftmi_cross_entropy, ftmi_mol_loss and their *_workspace_bytes; ftmi_run_chain;
+ * 21: ftmi_gemm_route, ftmi_conv1d_route, ftmi_conv_bank_route, ftmi_highway_route,
+ * ftmi_gemm_switches_digest; no existing signature changed). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -276,6 +278,50 @@ int ftmi_highway_split(const float *x, int64_t x_stride, int64_t M, int32_t C,
                        const float *b2, float *y, int64_t y_stride, int32_t mma,
                        uint32_t *status, int32_t split_k, float *split_ws,
                        ftmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Which kernel a conv / bank / highway launch takes (ABI 21).  The library decides it in one
+ * function, from the launch's arguments and the routing switches it reads from the
+ * environment on every call (FTMI_GEMM_SLAB, FTMI_GEMM_SLAB_MIN, FTMI_GEMM_SLAB_WS,
+ * FTMI_SLAB_K1_NMIN, FTMI_SLAB_PF, FTMI_SLAB_BAND, FTMI_GEMM_SKINNY, FTMI_SKINNY_CPB,
+ * FTMI_BANK_BALANCED, FTMI_BANK_WALK, FTMI_BANK_HALVES).  The queries below run that function
+ * for a caller that has to size a workspace before it launches: host only, no launch, no
+ * device call, no pointer dereferenced.  Each takes the arguments of its entry point (so the
+ * alignment and stride tests see the real pointers), returns that entry point's argument
+ * errors, and otherwise fills *route and returns FTMI_OK.
+ * ---------------------------------------------------------------------------------- */
+enum { FTMI_ROUTE_UNSUPPORTED = 0, /* the entry point would return FTMI_E_UNSUPPORTED */
+       FTMI_ROUTE_SKINNY, FTMI_ROUTE_SKINNY_BANK, /* weight-streaming few-row kernel / its
+                                                     balanced bank schedule */
+       FTMI_ROUTE_SLAB, FTMI_ROUTE_SLAB_WS, FTMI_ROUTE_SLAB_PF, /* 256 x 128 slab kernels */
+       FTMI_ROUTE_BANK_WALK,   /* pooled bank on at most 96 input channels */
+       FTMI_ROUTE_BANK_HALVES, /* the one-launch few-row bank: pass FTMI_BANK_HALVES */
+       FTMI_ROUTE_X6B_F16, FTMI_ROUTE_X6B_BF16, FTMI_ROUTE_X6, FTMI_ROUTE_F32 /* 128 x 128 tiles */ };
+typedef struct ftmi_gemm_route {
+  int32_t kernel;    /* FTMI_ROUTE_* */
+  int32_t split_k;   /* the split the kernel requires, to be passed with split_ws; 0: none
+                        required — the kernel takes whatever split_k its caller chooses (with
+                        split_k * rows * N floats) or none */
+  int64_t ws_floats; /* floats of split_ws for that split_k (FTMI_ROUTE_BANK_HALVES: the
+                        counters included, as ftmi_conv_bank_halves_ws_floats) */
+  int32_t pooled;    /* the FTMI_BANK_POOL / FTMI_BANK_Y_SPLIT store asked for is accepted */
+  int32_t band;      /* slab kernels: the column-band tile order (FTMI_SLAB_BAND), else 0 */
+} ftmi_gemm_route;
+/* args->split_k / split_ws are ignored. */
+int ftmi_conv1d_route(const ftmi_conv_args *args, ftmi_gemm_route *route);
+/* flags: FTMI_BANK_POOL | FTMI_BANK_Y_SPLIT | FTMI_BANK_X_SPLIT only. */
+int ftmi_conv_bank_route(const float *x, int64_t x_stride, int32_t B, int32_t T, int32_t Cin,
+                         const float *w, const void *w_split, int32_t K, int32_t Cout,
+                         const float *bn_scale, const float *bn_shift, float *y,
+                         int64_t y_stride, int32_t mma, uint32_t *status, int32_t flags,
+                         ftmi_gemm_route *route);
+int ftmi_highway_route(const float *x, int64_t x_stride, int64_t M, int32_t C,
+                       const float *w12, const void *w12_split, const float *b1,
+                       const float *b2, float *y, int64_t y_stride, int32_t mma,
+                       uint32_t *status, ftmi_gemm_route *route);
+/* 64-bit digest of the routing switches as the next launch would read them: equal digests,
+ * equal routes for equal arguments (a cached launch list is keyed by it). */
+uint64_t ftmi_gemm_switches_digest(void);
 
 /* CBHG highway stack in one launch (ABI 9; common_layers.py:110-115 + the GRU's input
  * projection): h = x W_pre^T (pre_highway, no bias), then L highway layers as ftmi_highway,

@@ -59,6 +59,34 @@ int main() {
   EXPECT(ftmi_highway(nullptr, 0, 1, 32, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, nullptr,
                       nullptr), FTMI_E_ARG);
   EXPECT(ftmi_highway(a, 32, 1, 40, a, a, a, a, buf + 1024, 40, 0, nullptr, nullptr), FTMI_E_SHAPE);
+  // the route queries: the entry points' argument checks, then the decision itself (host
+  // only: the environment scan, the GemmParams fill and route() run under the sanitizer)
+  ftmi_gemm_route rt;
+  EXPECT(ftmi_conv1d_route(nullptr, &rt), FTMI_E_ARG);
+  EXPECT(ftmi_conv1d_route(&ca, nullptr), FTMI_E_ARG);
+  EXPECT(ftmi_conv1d_route(&ca, &rt), FTMI_E_ARG);     // f16x3 without the split planes
+  ca.w_split = a;
+  EXPECT(ftmi_conv1d_route(&ca, &rt), FTMI_OK);
+  EXPECT(rt.kernel, FTMI_ROUTE_SKINNY);
+  ca.B = 64; ca.T = 200; ca.N = 256; ca.y_stride = 256; ca.k = 5; ca.pad = 2;
+  EXPECT(ftmi_conv1d_route(&ca, &rt), FTMI_OK);
+  EXPECT(rt.kernel, FTMI_ROUTE_SLAB_WS);
+  ca.B = 1; ca.T = 4; ca.N = 8; ca.y_stride = 8; ca.k = 1; ca.pad = 0; ca.w_split = nullptr;
+  EXPECT(ftmi_conv_bank_route(a, 64, 1, 120, 64, a, a, 16, 256, a, a, a, 4096, 2, nullptr, 0, &rt),
+         FTMI_OK);
+  EXPECT(rt.kernel, FTMI_ROUTE_BANK_HALVES);
+  EXPECT(ftmi_conv_bank_route(a, 64, 64, 200, 64, a, a, 16, 256, a, a, a, 4096, 2, nullptr,
+                              FTMI_BANK_POOL | FTMI_BANK_Y_SPLIT, &rt), FTMI_OK);
+  EXPECT(rt.pooled, 1);
+  EXPECT(ftmi_conv_bank_route(a, 64, 1, 120, 64, a, a, 16, 256, a, a, a, 4096, 2, nullptr,
+                              FTMI_BANK_HALVES, &rt), FTMI_E_ARG);  // not a query flag
+  EXPECT(ftmi_conv_bank_route(a, 64, 1, 120, 64, a, a, 16, 256, a, a, a, 4096, 2, nullptr, 0,
+                              nullptr), FTMI_E_ARG);
+  EXPECT(ftmi_highway_route(a, 32, 8, 32, a, a, a, a, buf + 1024, 32, 2, nullptr, &rt), FTMI_OK);
+  EXPECT(rt.split_k, 1);
+  EXPECT(ftmi_highway_route(a, 32, 8, 32, a, a, a, a, buf + 1024, 32, 2, nullptr, nullptr),
+         FTMI_E_ARG);
+  EXPECT(ftmi_gemm_switches_digest() == ftmi_gemm_switches_digest(), 1);
   // fused highway stack: L entries of the host pointer arrays are read, never more
   EXPECT(ftmi_highway_stack(nullptr, 80, 10, 80, 256, a, 0, nullptr, nullptr, nullptr, nullptr,
                             nullptr, 0, nullptr, 0, a, 256, nullptr, nullptr), FTMI_E_ARG);

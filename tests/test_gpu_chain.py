@@ -265,6 +265,33 @@ def test_plan_cache(monkeypatch):
     assert torch.equal(y, _per_op(monkeypatch, mod, x, 1.0))
 
 
+def test_routing_switch_builds_another_plan(monkeypatch):
+    """A routing switch of the library toggled between two calls (FTMI_GEMM_SKINNY: the 80
+    rows' convs leave the skinny kernel, so the recorded splits no longer hold) reaches the
+    plan cache through the library's digest: a second plan is recorded, the first one is not
+    replayed, and each call returns the bits of the per-op path under the same setting."""
+    from forwardtacotron_amd import chain
+    mod, x = _predictor(64, seed=12), _ids(2, 40)
+    monkeypatch.delenv('FTMI_GEMM_SKINNY', raising=False)
+    n = chain.BUILDS
+    first = mod.forward_bt(x, 1.3)
+    plan = _plan(mod, x)
+    assert chain.BUILDS == n + 1
+    ref = _per_op(monkeypatch, mod, x, 1.3)
+    monkeypatch.setenv('FTMI_GEMM_SKINNY', '0')
+    assert chain.cached_plan(mod, x) is None
+    second = mod.forward_bt(x, 1.3)
+    assert chain.BUILDS == n + 2 and _plan(mod, x) is not plan
+    replay = mod.forward_bt(x, 1.3)
+    ref0 = _per_op(monkeypatch, mod, x, 1.3)
+    monkeypatch.delenv('FTMI_GEMM_SKINNY')
+    assert _plan(mod, x) is plan and chain.BUILDS == n + 2
+    torch.cuda.synchronize()
+    assert torch.isfinite(ref).all() and float(ref.abs().max()) > 0
+    assert torch.equal(first, ref)
+    assert torch.equal(second, ref0) and torch.equal(replay, ref0)
+
+
 def test_probe_entry(preds):
     """Under a KernelProbe the chain is one entry with its ops' summed work."""
     from forwardtacotron_amd.probe import KernelProbe
