@@ -214,7 +214,17 @@ __device__ __forceinline__ void report_timeout(const RnnParams &p) {
 // workgroups at B = 64 as 16 units with 8 live sequences (legacy_nbl), with two thirds of
 // the MFMAs per wave and 128 cells per workgroup (waves 0-1 own them).  Measured at B = 64,
 // T = 1368: 1.11-1.12 against 1.39 us/step (tools/rnn_diag.py, profiles/r5_rnn_diag.txt).
-template <int CELL, int H, int U, int WK, int MODE, bool CST = false, int NBL = NB>
+// CR (cell rows; the CST forms of the LSTM at U = 16 and the GRU at U = 8): the W_hh rows of a
+// 16-row block are ordered unit-major (fragment row fr = unit 4 block + fr / 4, gate fr % 4;
+// the GRU's gate 3 is a zero row), so the four accumulator registers of lane (ls, lc) in block
+// i are the four gate sums of ONE cell (unit 4 i + ls, sequence lc).  Wave w owns block w and
+// its 64 cells (its fragments hold the blocks w, w + 1, .. mod 4, so acc[0] is its own in
+// every wave): it keeps its own K-split partial in registers and the waves exchange the other
+// partials as 16-byte words (3 ds_write_b128 + 3 ds_read_b128 per lane and step in place of
+// 16 + 16 four-byte accesses).  The sums are added in the same order (wk = 0..3), so every
+// value is bit-identical to the gate-major form.
+template <int CELL, int H, int U, int WK, int MODE, bool CST = false, int NBL = NB,
+          bool CR = false>
 __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
     const RnnParams p) {
   constexpr bool X6 = MODE != 0;  // 16x16x32 fragment layout (bf16x6 and f16x3)
@@ -242,20 +252,29 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
   static_assert(!CST || (H3 && !LOCAL && CPT == 1 && (U == 16 || U == 8)), "compute-wave h stores");
   static_assert(U != 8 || (CST && CELL == 0 && NBL == NB), "U = 8: the spread GRU's CST form");
   static_assert(NBL == NB || (NBL == 8 && !LOCAL), "live sequences per group");
+  static_assert(!CR || (CST && WK == 4 && NBL == NB && ((CELL == 1 && U == 16) || (CELL == 0 && U == 8))),
+                "cell rows: the LSTM at U = 16 and the GRU at U = 8, 4 units per row block");
   constexpr int RR = RB * 16;                     // reduction rows (dead ones included)
   constexpr float GSC = H3 ? H3_UNSCALE : 1.f;     // scale of the reduced W_hh h sums
 
-  __shared__ __attribute__((aligned(16))) float red[WK * RR * RED_STRIDE];
+  // K-split partials; CR: red[block][wave][lane] as 16-byte words
+  __shared__ __attribute__((aligned(16))) float red[CR ? RB * WK * 64 * 4 : WK * RR * RED_STRIDE];
   __shared__ __attribute__((aligned(16))) float hloc[LOCAL ? 2 * 16 * H : 4];
   // multi-workgroup groups: the new h slice and y values of this workgroup, handed from the
   // compute waves to the comm wave (cell c = seq * U + unit; float4 f = 4 units)
   __shared__ __attribute__((aligned(16))) float hstage[LOCAL ? 4 : CELLS];
   __shared__ __attribute__((aligned(16))) float ystage[LOCAL ? 4 : CELLS];
+  // CR: a step's input projections on their way from the fetching thread to the cell's owner,
+  // one word (G gates) per cell at [unit * 17 + sequence] (the pitch keeps both sides off
+  // each other's banks)
+  __shared__ __attribute__((aligned(16))) float gxs[CR ? U * 17 * 4 : 4];
   __shared__ int s_abort, s_group, s_bi, s_mode;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wk = wave % WK, wr = wave / WK;
   const int ls = lane >> 4, lc = lane & 15;
+  // the wave index as a scalar (CR: the block whose cells this wave owns)
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
   // ---- group assignment (census for the XCD-local mode) ----------------------------
   if (tid == 0) {
@@ -394,9 +413,12 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
 #pragma unroll
   for (int i = 0; i < RBW; ++i) {
     const int lrow0 = (wr * RBW + i) * 16 + lc;
-    const bool rlive = lrow0 < R;  // a dead row (R % 16 != 0) multiplies zeros
+    // CR: fragment i holds block (wave + i) % RB, the wave's own block first; fragment row lc
+    // of block b = (unit 4 b + lc / 4, gate lc % 4)
+    const bool rlive = CR ? (lc & 3) < G : lrow0 < R;  // a dead row multiplies zeros
     const int lrow = rlive ? lrow0 : 0;
-    const int grow = (lrow / U) * H + u0 + (lrow % U);
+    const int grow = CR ? (rlive ? (lc & 3) : 0) * H + u0 + 4 * ((wave_u + i) & (RB - 1)) + (lc >> 2)
+                        : (lrow / U) * H + u0 + (lrow % U);
     const float *src = wdir + (size_t)grow * H + wk * KW;
     if constexpr (X6) {
 #pragma unroll
@@ -432,14 +454,15 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
   if (wbad && p.status) atomicOr(p.status, 2u);
 
   // ---- per-thread cells: cell c = tid + 256*j -> (unit u = c % U, seq b = c / U) ------
+  // CR: lane (ls, lc) of wave w -> (unit 4 w + ls, seq lc), the cell its acc[0] holds
   int cu[CPT], cb[CPT], cbl[CPT], len[CPT], hxo[CPT];
   bool cvalid[CPT];
   float hstate[CPT], cstate[CPT], bhh[CPT][G];
 #pragma unroll
   for (int j = 0; j < CPT; ++j) {
     const int c = tid + 256 * j;
-    cu[j] = c % U;
-    const int bl = c / U;
+    cu[j] = CR ? (4 * wave + ls) % U : c % U;  // (% U: the waves without cells, U = 8)
+    const int bl = CR ? lc : c / U;
     cbl[j] = bl;
     cb[j] = chunk * NBL + bl;
     cvalid[j] = bl < NBL && cb[j] < p.B;
@@ -466,14 +489,47 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
     }
     hxo[j] = ((kwv * NL + idx4) * 64 + ln) * 4 + e;
   }
+  // The cell whose input projections this thread FETCHES: its own — except CR, which keeps the
+  // gate-major form's assignment (consecutive lanes = consecutive units of a sequence: U * 4
+  // bytes of a projection row per gate; by the owners' lanes a load would touch 16 rows for 16
+  // bytes each, measured + 0.1 us/step on the U = 8 GRU) and hands the values to the owner
+  // through LDS, one 16-byte word per cell (gxs)
+  int lu[CPT], lbl[CPT], lb[CPT];
+  bool lvalid[CPT];
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) {
+    const int c = tid + 256 * j;
+    lu[j] = CR ? c % U : cu[j];
+    lbl[j] = CR ? c / U : cbl[j];
+    lb[j] = chunk * NBL + lbl[j];
+    lvalid[j] = lbl[j] < NBL && lb[j] < p.B;
+  }
 
   // ---- h operand source ----------------------------------------------------------------
   const int slab = 16 * H;
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(p.hx, (short)0, 0x7FFFFFF0, 0x00020000);
   const unsigned hoff = (unsigned)((gglob * slab + wk * NL * 256 + lane * 4) * 4);
   const int hx_par = p.ngroups_total * slab * 4;  // bytes between the two parity halves
+  // CR: 16-byte word indices into red[block][wave][lane]: where fragment i's partial goes, and
+  // the three other waves' partials of this wave's own block in ascending wk (a wave without
+  // cells reads a block it never uses)
+  int red_w[RBW], red_r[3];
+#pragma unroll
+  for (int i = 0; i < RBW; ++i) red_w[i] = (((wave_u + i) & (RB - 1)) * WK + wave_u) * 64 + lane;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    red_r[k] = ((wave_u & (RB - 1)) * WK + k + (k >= wave_u ? 1 : 0)) * 64 + lane;
   unsigned cst_off = 0;  // CST: the exchange offset of stage chunk 16 wave + lane
-  if constexpr (CST) {
+  if constexpr (CR) {
+    // lane l < 32 stores the 8-byte piece (sequence l % 16, this wave's 4 units, plane l / 16):
+    // one half of the 16-byte chunk (sequence, 8 units, plane) the consumers load
+    const int bl = lane & 15, plane = (lane >> 4) & 1, c0 = (4 * wave) % U;
+    const int k0 = u0 + (c0 / 8) * 8;
+    const int kwv = k0 / KW, r = k0 % KW, q = r % 32;
+    const int ln = (q >> 3) * 16 + bl;
+    cst_off = (unsigned)((gglob * 16 * H * 2 + ((kwv * NL + (r / 32) * 2 + plane) * 64 + ln) * 8 +
+                          c0 % 8) * 2);
+  } else if constexpr (CST) {
     const int f = 16 * wave + (lane & 15);
     const int bl = f / (U / 4), rem = f % (U / 4), plane = rem & 1;
     const int k0 = u0 + (rem >> 1) * 8;
@@ -491,7 +547,7 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
   size_t brow[CPT];
 #pragma unroll
   for (int j = 0; j < CPT; ++j) {
-    const int b = cvalid[j] ? cb[j] : 0;
+    const int b = lvalid[j] ? lb[j] : 0;
     iptr[j] = p.index ? p.index + (size_t)b * p.T : (const int32_t *)p.ws;
     brow[j] = (size_t)b * p.T_src;
   }
@@ -511,7 +567,7 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
       const float *row = src >= 0 ? xcol + (brow[j] + src) * p.xp_stride : zcol;
       if (RNN_DIAG(p) & 1) row = zcol;  // timing experiment: L2-hot rows
 #pragma unroll
-      for (int gi = 0; gi < G; ++gi) g[j][gi] = row[gi * H + cu[j]];
+      for (int gi = 0; gi < G; ++gi) g[j][gi] = row[gi * H + lu[j]];
     }
   };
   float g0[CPT][G], g1[CPT][G], g2[CPT][G];
@@ -534,6 +590,13 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
   auto step = [&](int t, const float (&gx)[CPT][G], float (&gnext)[CPT][G],
                   const int (&inext)[CPT], int (&iload)[CPT]) -> bool {
     const int tt = frame(t);
+    if constexpr (CR) {
+      // this step's projections (fetched two steps ago) to the cells' owners, who read them
+      // after barrier B; the previous step's were consumed before its closing barrier
+      if (!(HALFCELL && tid >= CELLS))
+        ((f32x4 *)gxs)[lu[0] * 17 + lbl[0]] =
+            (f32x4){gx[0][0], gx[0][1], gx[0][2], G > 3 ? gx[0][G - 1] : 0.f};
+    }
     STAMP(0);
     // h_{t-1} operand: NL float4 per lane (fragment order), zero at t = 0.  f16x3 groups of
     // several workgroups exchange h pre-split: hr[2 ks] = 8 heads, hr[2 ks + 1] = 8 scaled
@@ -681,14 +744,39 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
         for (int i = 0; i < RBW; ++i)
           acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[i][kb], hv[kb], acc[i], 0, 0, 0);
     }
+    if constexpr (CR) {
+      // one 16-byte word per block of another wave's cells: fragments 1.. (and fragment 0 of
+      // the GRU's waves 2-3, which own no cells)
+      if (RB < WK && wave_u >= RB) ((f32x4 *)red)[red_w[0]] = acc[0];
 #pragma unroll
-    for (int i = 0; i < RBW; ++i)
+      for (int i = 1; i < RBW; ++i) ((f32x4 *)red)[red_w[i]] = acc[i];
+    } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        red[(wk * RR + (wr * RBW + i) * 16 + ls * 4 + e) * RED_STRIDE + lc] = acc[i][e];
+      for (int i = 0; i < RBW; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          red[(wk * RR + (wr * RBW + i) * 16 + ls * 4 + e) * RED_STRIDE + lc] = acc[i][e];
+    }
     __syncthreads();
     if (!LOCAL && s_abort) return false;  // a wave timed out acquiring h_{t-1}
     STAMP(3);
+    // CR: the four gate sums of this lane's cell: the K-split partials added in the order
+    // wk = 0..3, ((p0 + p1) + p2) + p3, with this wave's own register partial as p_wave and
+    // a, b, c the other three in ascending wk (waves 0 and 1 differ only in the operand order
+    // of the first addition, which is commutative)
+    f32x4 csum = (f32x4){0.f, 0.f, 0.f, 0.f}, cgx = csum;
+    if constexpr (CR) {
+      cgx = ((const f32x4 *)gxs)[cu[0] * 17 + lc];
+      const f32x4 a = ((const f32x4 *)red)[red_r[0]];
+      const f32x4 b = ((const f32x4 *)red)[red_r[1]];
+      const f32x4 c = ((const f32x4 *)red)[red_r[2]];
+      if (RB < WK || wave_u < 2)
+        csum = ((acc[0] + a) + b) + c;
+      else if (wave_u == 2)
+        csum = ((a + b) + acc[0]) + c;
+      else
+        csum = ((a + b) + c) + acc[0];
+    }
 
     // cell update
 #pragma unroll
@@ -698,12 +786,17 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
       float gs[G], gi[G];
 #pragma unroll
       for (int g = 0; g < G; ++g) {
-        const int row = g * U + cu[j];
-        float sum = red[row * RED_STRIDE + bl];
+        float sum;
+        if constexpr (CR) {
+          sum = csum[g];
+        } else {
+          const int row = g * U + cu[j];
+          sum = red[row * RED_STRIDE + bl];
 #pragma unroll
-        for (int w = 1; w < WK; ++w) sum += red[(w * RR + row) * RED_STRIDE + bl];
+          for (int w = 1; w < WK; ++w) sum += red[(w * RR + row) * RED_STRIDE + bl];
+        }
         gs[g] = sum;  // H3: 2^11 (W_hh h)
-        gi[g] = gx[j][g];
+        gi[g] = CR ? cgx[g] : gx[j][g];
       }
       float hn;
       if (RNN_DIAG(p) & 128) {  // 128: no transcendentals (timing)
@@ -741,11 +834,18 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
             _Float16, (unsigned short)((__builtin_bit_cast(unsigned short,
                                                            (_Float16)((hn - (float)h16) * H3_SCALE)) &
                                         0xFFFEu) | tg));
-        // chunk (seq, 8 units, plane) of halves: the comm wave's 16-B order
         _Float16 *hs16 = (_Float16 *)hstage;
-        const int base = ((bl * (U / 8) + cu[j] / 8) * 2) * 8 + (cu[j] % 8);
-        hs16[base] = h16;
-        hs16[base + 8] = t16;
+        if constexpr (CR) {
+          // this wave's 32 pieces (plane, sequence) of 4 units, 8 bytes each, in the order
+          // its lanes 0..31 store them
+          hs16[wave * 128 + lc * 4 + ls] = h16;
+          hs16[wave * 128 + 64 + lc * 4 + ls] = t16;
+        } else {
+          // chunk (seq, 8 units, plane) of halves: the comm wave's 16-B order
+          const int base = ((bl * (U / 8) + cu[j] / 8) * 2) * 8 + (cu[j] % 8);
+          hs16[base] = h16;
+          hs16[base + 8] = t16;
+        }
       } else if constexpr (!LOCAL) {
         // multi-workgroup groups: h_t carries the step tag in its mantissa LSB (a <= 1 ulp
         // change); the same tagged value is the state, the exchange and the layer output
@@ -764,7 +864,22 @@ __global__ __launch_bounds__(H / U == 1 ? 256 : 320, 1) void rnn_bidir_kernel(
         ystage[c] = yout;
       }
     }
-    if constexpr (CST) {
+    if constexpr (CR) {
+      // this wave's cells (units 4 wave .. 4 wave + 3, all 16 sequences) are 32 tagged pieces
+      // (sequence, 4 units, plane) of 8 bytes: read back (same wave, LDS in order) and store
+      // to the halves of the 16-byte chunks the consumers load (4-byte accesses are
+      // single-copy atomic, which is all the tag protocol needs)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (lane < 32 && !(HALFCELL && tid >= CELLS)) {
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 v = *(const u32x2 *)((const _Float16 *)hstage + wave * 128 + lane * 4);
+        if (xcd_mode)
+          __builtin_amdgcn_raw_buffer_store_b64(v, rsrc, cst_off, (t & 1) * hx_par, 0);
+        else
+          __builtin_amdgcn_raw_buffer_store_b64(v, rsrc, cst_off, (t & 1) * hx_par, 16);
+      }
+    } else if constexpr (CST) {
       // this wave's cells (sequences 4 wave .. 4 wave + 3, all 16 units) are the stage's
       // chunks 16 wave .. 16 wave + 15: read back (same wave, LDS in order) and store
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1060,7 +1175,8 @@ int launch_gemv(RnnParams p, int max_blocks, hipStream_t s) {
   return FTMI_OK;
 }
 
-template <int CELL, int H, int U, int WK, int MODE, bool CST = false, int NBL = NB>
+template <int CELL, int H, int U, int WK, int MODE, bool CST = false, int NBL = NB,
+          bool CR = false>
 int launch_rnn(RnnParams p, int nchunks, int max_blocks, hipStream_t s) {
   if (NBL != NB) {  // chunks of NBL sequences (the caller counted chunks of NB)
     nchunks = (p.B + NBL - 1) / NBL;
@@ -1087,10 +1203,10 @@ int launch_rnn(RnnParams p, int nchunks, int max_blocks, hipStream_t s) {
     int nblk = p.ngroups * BPG;
     if (BPG > 1 && pad_env && p.xcd_local && p.ngroups < 8 && 8 * BPG <= max_blocks)
       nblk = 8 * BPG;
-    if (int rc = ftmi_resident_ok((const void *)rnn_bidir_kernel<CELL, H, U, WK, MODE, CST, NBL>,
+    if (int rc = ftmi_resident_ok((const void *)rnn_bidir_kernel<CELL, H, U, WK, MODE, CST, NBL, CR>,
                                   nblk, BPG == 1 ? 256 : 320, 0))
       return rc;
-    hipLaunchKernelGGL((rnn_bidir_kernel<CELL, H, U, WK, MODE, CST, NBL>), dim3(nblk),
+    hipLaunchKernelGGL((rnn_bidir_kernel<CELL, H, U, WK, MODE, CST, NBL, CR>), dim3(nblk),
                        dim3(BPG == 1 ? 256 : 320), 0, s, p);
     FTMI_CHECK_LAUNCH();
   }
@@ -1119,12 +1235,9 @@ static bool gemv_path(int cell, int B, int H) {
   const int env = v ? atoi(v) : 1;
   return env && B <= GV_MAXB && ((cell == 1 && H == 512) || (cell == 0 && (H == 64 || H == 128 || H == 256)));
 }
-static int xcd_local_env() {
-  static const int v = [] {
-    const char *e = getenv("FTMI_RNN_XCD_LOCAL");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
+static int xcd_local_env() {  // read per call: tests switch it
+  const char *e = getenv("FTMI_RNN_XCD_LOCAL");
+  return e ? atoi(e) : 1;
 }
 
 // hidden units per workgroup of the instance ftmi_rnn_bidir dispatches (see there)
@@ -1144,6 +1257,13 @@ static int rnn_units(int cell, int H, int mma) {
 // 1.535 (barrier C and the stage read leave the hand-off's critical path)
 static bool cst_enabled() {
   const char *v = getenv("FTMI_RNN_CSTORE");
+  return !(v && atoi(v) == 0);
+}
+// FTMI_RNN_CELLROWS=0 (read per call: the A/B and tests switch it) keeps the gate-major W_hh
+// rows and the four-byte K-split reduction for the CST LSTM (U = 16) and the U = 8 GRU
+// (rnn_bidir_kernel CR); bit-identical results either way
+static bool cellrows_enabled() {
+  const char *v = getenv("FTMI_RNN_CELLROWS");
   return !(v && atoi(v) == 0);
 }
 // live sequences per group of a spread f16x3 GRU on rnn_bidir_kernel: 8 when twice the groups
@@ -1258,10 +1378,12 @@ static int rnn_setup(RnnParams &p, int B, int T, int H, int cell, const float *w
   return FTMI_OK;
 }
 
-// first-poll delay of the U = 8 spread GRU (see rnn_setup)
+// first-poll delay of the U = 8 spread GRU (see rnn_setup): 6 on the gate-major chain, 3 on
+// the cell-row chain, whose producers store earlier in the step (c3, two interleaved rounds of
+// tools/rnn_diag.py: 0.99-1.00 at 2..4 against 1.04 us/step at 6)
 static int u8_psleep() {
   const char *v = getenv("FTMI_RNN_PSLEEP");
-  return v ? atoi(v) : 6;
+  return v ? atoi(v) : (cellrows_enabled() ? 3 : 6);
 }
 
 extern "C" int ftmi_rnn_bidir(int32_t cell, int32_t B, int32_t T, int32_t H, const float *xp,
@@ -1336,9 +1458,12 @@ extern "C" int ftmi_rnn_bidir(int32_t cell, int32_t B, int32_t T, int32_t H, con
     const bool nb8 = legacy_nbl(cell, B, H, mma, spread, maxb) == 8;
     if (u8_path(cell, B, H, mma, spread, maxb)) {
       p.psleep = u8_psleep();
-      return launch_rnn<0, 256, 8, 4, 2, true>(p, nchunks, maxb, s);
+      return cellrows_enabled() ? launch_rnn<0, 256, 8, 4, 2, true, NB, true>(p, nchunks, maxb, s)
+                                : launch_rnn<0, 256, 8, 4, 2, true>(p, nchunks, maxb, s);
     }
-    if (cell == 1) return launch_rnn<1, 512, 16, 4, 2, true>(p, nchunks, maxb, s);
+    if (cell == 1)
+      return cellrows_enabled() ? launch_rnn<1, 512, 16, 4, 2, true, NB, true>(p, nchunks, maxb, s)
+                                : launch_rnn<1, 512, 16, 4, 2, true>(p, nchunks, maxb, s);
     return nb8 ? launch_rnn<0, 256, 16, 4, 2, true, 8>(p, nchunks, maxb, s)
                : launch_rnn<0, 256, 16, 4, 2, true>(p, nchunks, maxb, s);
   }
