@@ -21,7 +21,7 @@ _lib = None
 
 c_int, c_int64, c_float, c_void_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 P = c_void_p  # every device pointer travels as void*
-ABI_VERSION = 21
+ABI_VERSION = 22
 MMA_F32, MMA_BF16X6, MMA_F16X3 = 0, 1, 2
 
 
@@ -49,6 +49,17 @@ class GemmRoute(ctypes.Structure):
  ROUTE_BANK_WALK, ROUTE_BANK_HALVES, ROUTE_X6B_F16, ROUTE_X6B_BF16, ROUTE_X6, ROUTE_F32) = range(12)
 ROUTE_SKINNIES = (ROUTE_SKINNY, ROUTE_SKINNY_BANK)
 ROUTE_SLABS = (ROUTE_SLAB, ROUTE_SLAB_WS, ROUTE_SLAB_PF, ROUTE_BANK_WALK)
+
+
+class RnnRoute(ctypes.Structure):
+    """Mirror of ftmi_rnn_route_t (include/ftmi.h): kernel and grid of an ftmi_rnn_bidir call."""
+    _fields_ = [(n, c_int) for n in (
+        'status', 'kernel', 'cell', 'H', 'units', 'wk', 'mode', 'cst', 'nbl', 'cr', 'kseg', 'nbv',
+        'threads', 'wg_per_group', 'groups', 'groups_per_pass', 'passes', 'first_blocks',
+        'xcd_local', 'pad', 'psleep', 'cus')]
+
+
+RNN_KERNEL_NONE, RNN_KERNEL_GEMV, RNN_KERNEL_BIDIR = range(3)  # include/ftmi.h FTMI_RNN_KERNEL_*
 
 
 class WaveRNNArgs(ctypes.Structure):
@@ -144,6 +155,8 @@ SIGNATURES = {
     'ftmi_rnn_workspace_bytes': (c_int64, [c_int, c_int, c_int]),
     'ftmi_rnn_error_offset': (c_int64, [c_int]),
     'ftmi_rnn_blocks': (c_int, [c_int, c_int, c_int, c_int]),
+    'ftmi_rnn_route': (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(RnnRoute)]),
+    'ftmi_rnn_switches_digest': (ctypes.c_uint64, []),
     'ftmi_set_rnn_spin_limit': (ctypes.c_uint32, [ctypes.c_uint32]),
     'ftmi_rnn_bidir': (c_int, [c_int, c_int, c_int, c_int, P, c_int64, c_int, P, P, P, P, P,
                                c_float, P, c_int64, c_int, P, P, P]),

@@ -247,7 +247,9 @@ def _base(t: torch.Tensor):
 def policy_key():
     """Everything besides the shape and the weights that the per-op path's choices read: a
     change of any builds another plan.  The library's routing switches enter as its own
-    digest of them (ftmi_gemm_switches_digest), so none is listed here."""
+    digest of them (ftmi_gemm_switches_digest), so none is listed here.  The recurrences'
+    switches (ftmi_rnn_switches_digest) need no place in it: a plan records the ftmi_rnn_bidir
+    call, not its kernel, and the replayed call reads them itself."""
     return (ops.MMA, ops.RNN_MMA, ops._FORCED[-1] if ops._FORCED else None, bool(ops._COMPACT),
             _lib.load().ftmi_gemm_switches_digest())
 

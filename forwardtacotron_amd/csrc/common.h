@@ -1,9 +1,14 @@
 // Internal helpers shared by the ftmi HIP translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include "../../include/ftmi.h"
+
+extern char **environ;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -35,6 +40,35 @@ static inline int ftmi_resident_ok(const void *kernel, int grid, int block, size
   }
   if (per <= 0) return FTMI_E_UNSUPPORTED;
   return (int64_t)per * ftmi_resident_cus() >= grid ? FTMI_OK : FTMI_E_UNSUPPORTED;
+}
+
+// Routing switches (gemm.hip Switches, rnn.hip RnnSwitches).  S holds one int64_t per switch
+// and then `uint64_t digest` (no padding before it); a table of ftmi_switch<S> has one line
+// per switch: a switch added to the table is read, per call, and in the digest without more.
+template <class S>
+struct ftmi_switch {
+  const char *name;
+  int64_t S::*field;
+  int64_t def;  // -1 by convention: the code's own rule
+};
+// One pass over the environment (a launch costs one scan, not a getenv per switch); the
+// digest is FNV-1a over the bytes before `digest`.
+template <class S, size_t N>
+static inline S ftmi_read_switches(const ftmi_switch<S> (&table)[N]) {
+  S sw = {};
+  for (const ftmi_switch<S> &d : table) sw.*d.field = d.def;
+  for (char **e = environ; e && *e; ++e) {
+    if (strncmp(*e, "FTMI_", 5) != 0) continue;
+    const char *eq = strchr(*e, '=');
+    if (!eq) continue;
+    const size_t n = (size_t)(eq - *e);
+    for (const ftmi_switch<S> &d : table)
+      if (strlen(d.name) == n && strncmp(*e, d.name, n) == 0) sw.*d.field = atoll(eq + 1);
+  }
+  sw.digest = 0xcbf29ce484222325ull;
+  for (size_t i = 0; i < offsetof(S, digest); ++i)
+    sw.digest = (sw.digest ^ ((const unsigned char *)&sw)[i]) * 0x100000001b3ull;
+  return sw;
 }
 
 __device__ __forceinline__ float ftmi_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }

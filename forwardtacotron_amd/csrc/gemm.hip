@@ -38,13 +38,7 @@
 // < 2^-22 relative.  The only range limit is |a| < 65504 for the activations: an overflow
 // makes the accumulator non-finite, which the epilogue reports through *status (bit 0);
 // the model layer then recomputes the call on the fp32 path.
-#include <stddef.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include "common.h"
-
-extern char **environ;
 
 namespace {
 
@@ -3719,17 +3713,13 @@ struct Switches {
   int64_t bank_halves;    // FTMI_BANK_HALVES=0: the few-row bank on the skinny kernel + finish
   uint64_t digest;        // FNV-1a of the fields above
 };
-struct SwitchDef {
-  const char *name;
-  int64_t Switches::*field;
-  int64_t def;  // -1: the kernel's own rule (slab_kernel, bank_walk_ok)
-};
+// (a default of -1: the kernel's own rule — slab_kernel, bank_walk_ok)
 // column bands of 2 (slab_tile): tools/gemm_one.py under rocprofv3, band 0 -> 2: c5 FFN conv
 // 1179 -> 1147 us (L2->fabric reads 913 -> 662 MB per launch), c3 prenet bank 803 -> 713,
 // postnet bank 710 -> 683, LSTM input projection 305 -> 297; proj1 (2 column tiles) unchanged.
 // FTMI_GEMM_SLAB_MIN = 0: taking the slab for every eligible shape measured fastest on c3
 // (10.01 vs 10.19 ms/step with an 8 GMAC bar); tests use it to cover both kernels.
-const SwitchDef SWITCHES[] = {
+const ftmi_switch<Switches> SWITCHES[] = {
     {"FTMI_GEMM_SLAB", &Switches::slab, 1},
     {"FTMI_GEMM_SLAB_MIN", &Switches::slab_min, 0},
     {"FTMI_GEMM_SLAB_WS", &Switches::slab_ws, -1},
@@ -3743,23 +3733,7 @@ const SwitchDef SWITCHES[] = {
     {"FTMI_BANK_HALVES", &Switches::bank_halves, 1},
 };
 
-// One pass over the environment (a launch costs one scan, not a getenv per switch)
-static Switches read_switches() {
-  Switches sw = {};
-  for (const SwitchDef &d : SWITCHES) sw.*d.field = d.def;
-  for (char **e = environ; e && *e; ++e) {
-    if (strncmp(*e, "FTMI_", 5) != 0) continue;
-    const char *eq = strchr(*e, '=');
-    if (!eq) continue;
-    const size_t n = (size_t)(eq - *e);
-    for (const SwitchDef &d : SWITCHES)
-      if (strlen(d.name) == n && strncmp(*e, d.name, n) == 0) sw.*d.field = atoll(eq + 1);
-  }
-  sw.digest = 0xcbf29ce484222325ull;
-  for (size_t i = 0; i < offsetof(Switches, digest); ++i)
-    sw.digest = (sw.digest ^ ((const unsigned char *)&sw)[i]) * 0x100000001b3ull;
-  return sw;
-}
+static Switches read_switches() { return ftmi_read_switches(SWITCHES); }
 
 // What route() decides: the kernel family (FTMI_ROUTE_*), the split that family requires with
 // the floats of split_ws that go with it (0: none required — the kernel takes whatever split

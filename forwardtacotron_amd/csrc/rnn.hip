@@ -1150,68 +1150,168 @@ __global__ __launch_bounds__((CELL ? 4 : 3) * U / GV_RPT * KSEG) void rnn_gemv_k
   }
 }
 
-template <int CELL, int H, int U, int KSEG = GV_KSEG>
-int launch_gemv(RnnParams p, int max_blocks, hipStream_t s) {
-  constexpr int BPG = H / U;
-  constexpr int NT = (CELL ? 4 : 3) * U / GV_RPT * KSEG;
-  if (8 * BPG > max_blocks) return FTMI_E_UNSUPPORTED;
-  p.chunk0 = 0;
-  p.ngroups = 2;
-  // one direction's BPG workgroups per XCD (the census seats direction x on XCD x; the
-  // other XCDs' workgroups retire after the census barrier)
-  const int nblk = p.xcd_local ? 8 * BPG : 2 * BPG;
-#define FTMI_GEMV_LAUNCH(NBV_)                                                             \
-  if (int rc = ftmi_resident_ok((const void *)rnn_gemv_kernel<CELL, H, U, NBV_, KSEG>, nblk, NT, 0)) \
-    return rc;                                                                               \
-  hipLaunchKernelGGL((rnn_gemv_kernel<CELL, H, U, NBV_, KSEG>), dim3(nblk), dim3(NT), 0, s, p); \
-  break;
-  switch (p.B) {
-    case 1: FTMI_GEMV_LAUNCH(1)
-    case 2: FTMI_GEMV_LAUNCH(2)
-    default: FTMI_GEMV_LAUNCH(4)
+// ---------------------------------------------------------------------------------------
+// Kernel selection, as gemm.hip's: read_rnn_switches() reads every switch, per call, into one
+// struct; rnn_route() decides kernel and grid from (cell, B, H, mma, spread, CUs) and that
+// struct alone (no device, no pointer, no launch); ftmi_rnn_bidir looks the decision up in
+// RNN_KERNELS and issues it; ftmi_rnn_route / ftmi_rnn_blocks hand the same decision out.
+
+// Every field an int64_t, one line of RNN_SWITCHES each (ftmi_read_switches, common.h)
+struct RnnSwitches {
+  int64_t gemv;       // FTMI_RNN_GEMV=0: B <= GV_MAXB stays on the MFMA kernel
+  int64_t gemv_kseg;  // FTMI_RNN_GEMV_KSEG=8: 8 k-segments per row for H = 512 / 256 too
+  int64_t xcd_local;  // FTMI_RNN_XCD_LOCAL=0: no census, groups by blockIdx
+  int64_t pad;        // FTMI_RNN_PAD=0: fewer than 8 groups are not padded to one per XCD
+  int64_t u64;        // FTMI_RNN_U64=64: the f16x3 H = 64 GRU as one workgroup per group
+  int64_t cstore;     // FTMI_RNN_CSTORE=0: the comm wave stores h (no CST forms)
+  int64_t cellrows;   // FTMI_RNN_CELLROWS=0: gate-major W_hh rows (no CR forms); same bits
+  int64_t nb;         // FTMI_RNN_NB=16: a spread GRU keeps 16 live sequences per group
+  int64_t u8;         // FTMI_RNN_U8=0: the spread postnet GRU keeps 16-unit workgroups
+  int64_t psleep;     // FTMI_RNN_PSLEEP: s_sleep(1) count before a step's first h poll
+  uint64_t digest;    // FNV-1a of the fields above
+};
+const ftmi_switch<RnnSwitches> RNN_SWITCHES[] = {
+    {"FTMI_RNN_GEMV", &RnnSwitches::gemv, 1},
+    {"FTMI_RNN_GEMV_KSEG", &RnnSwitches::gemv_kseg, 16},
+    {"FTMI_RNN_XCD_LOCAL", &RnnSwitches::xcd_local, 1},
+    {"FTMI_RNN_PAD", &RnnSwitches::pad, 1},
+    {"FTMI_RNN_U64", &RnnSwitches::u64, 32},
+    {"FTMI_RNN_CSTORE", &RnnSwitches::cstore, 1},
+    {"FTMI_RNN_CELLROWS", &RnnSwitches::cellrows, 1},
+    {"FTMI_RNN_NB", &RnnSwitches::nb, 8},
+    {"FTMI_RNN_U8", &RnnSwitches::u8, 1},
+    {"FTMI_RNN_PSLEEP", &RnnSwitches::psleep, -1},  // -1: unset (rnn_route's own rule)
+};
+static RnnSwitches read_rnn_switches() { return ftmi_read_switches(RNN_SWITCHES); }
+
+typedef ftmi_rnn_route_t RnnRoute;
+constexpr int GV_MAXB = 4;  // B <= GV_MAXB: the exact-fp32 GEMV recurrence (rnn_gemv_kernel)
+
+// the kernel forms: GRU H 64 / 128 / 256, LSTM H 512
+static bool rnn_shape_ok(int cell, int H) {
+  return cell == 1 ? H == 512 : (cell == 0 && (H == 64 || H == 128 || H == 256));
+}
+
+// Workgroups of one pass of `ngroups` groups.  Fewer than 8 groups (small batches): the grid
+// is padded to one group's workgroups per XCD so that each group can run inside one XCD (the
+// census picks the layout; the other XCDs' workgroups retire after the census barrier).
+static int rnn_pass_blocks(const RnnRoute &r, int ngroups) {
+  const int bpg = r.wg_per_group;
+  const bool pad = r.kernel == FTMI_RNN_KERNEL_GEMV
+                       ? r.xcd_local != 0
+                       : bpg > 1 && r.pad && r.xcd_local && ngroups < 8 && 8 * bpg <= r.cus;
+  return (pad ? 8 : ngroups) * bpg;
+}
+
+static RnnRoute rnn_route(int cell, int B, int H, int mma, bool spread, int cus,
+                          const RnnSwitches &sw) {
+  RnnRoute r = {};
+  r.status = FTMI_E_UNSUPPORTED;
+  r.cell = cell;
+  r.H = H;
+  r.cus = cus;
+  r.xcd_local = (int)sw.xcd_local;
+  r.pad = sw.pad != 0;
+  // first-poll delay: interleaved A/B at c3 (tools/rnn_env_ab.py, two boxes): 3 -> LSTM 1.55
+  // -> 1.52-1.54, postnet GRU 1.32 -> 1.27 us/step; 6 made the LSTM slower again (1.58-1.61)
+  r.psleep = sw.psleep < 0 ? 3 : (int)sw.psleep;
+  if (B <= 0 || !rnn_shape_ok(cell, H)) return r;
+  if (sw.gemv && B <= GV_MAXB) {  // any mma: it is exact
+    // H = 512 / 256: 16 k-segments per row (512 / 384 threads, half the FMA chain per thread):
+    // c2 LSTM 1.26 -> 1.17-1.18, postnet GRU 1.01 -> 0.96-0.97 us/step (tools/rnn_diag.py,
+    // two interleaved rounds; 32 segments: 1.32-1.34 / 1.07-1.08)
+    r.kernel = FTMI_RNN_KERNEL_GEMV;
+    r.units = 16;
+    r.kseg = H >= 256 && sw.gemv_kseg != 8 ? 16 : GV_KSEG;
+    r.nbv = B <= 2 ? B : 4;
+    r.threads = (cell ? 4 : 3) * r.units / GV_RPT * r.kseg;
+    r.wg_per_group = H / r.units;
+    r.groups = r.groups_per_pass = 2;  // the two directions of one chunk
+    r.passes = 1;
+    r.first_blocks = rnn_pass_blocks(r, 2);
+    // one direction's workgroups per XCD must fit, whichever layout runs
+    if (8 * r.wg_per_group <= cus) r.status = FTMI_OK;
+    return r;
   }
-#undef FTMI_GEMV_LAUNCH
+  r.kernel = FTMI_RNN_KERNEL_BIDIR;
+  r.mode = mma;
+  r.units = 16;
+  r.wk = 4;
+  r.nbl = NB;
+  if (H == 64) {
+    // f16x3: 32 units per workgroup (2 per group, h exchanged through L2) 1.19 us/step against
+    // 1.45 for one workgroup per group (h in LDS) at B = 64
+    r.units = mma == 2 && sw.u64 == 32 ? 32 : 64;
+    r.wk = mma ? 2 : 4;
+  } else if (H != 128 && mma == 2 && sw.cstore) {
+    // H = 256 / 512, f16x3: the compute waves store their own h (CST; measured at c3: postnet
+    // GRU 1.315 -> 1.116 us/step, LSTM 1.55 -> 1.535).  H = 128 keeps 16 units without it:
+    // 1.04 us/step against 2.33 with 64 units at B = 64
+    r.cst = 1;
+    const bool post = spread && cell == 0;  // the spread postnet GRU
+    const int groups = 2 * ((B + NB - 1) / NB);
+    if (post && sw.u8 && (groups < 8 ? 8 : groups) * (H / 8) <= cus) {
+      // workgroups of 8 units while every group's workgroups fit one per CU (B <= 64 on 256
+      // CUs).  Rejected and removed: U = 8 for the LSTM (two workgroups of a group per CU: no
+      // MFMA time saved, and the census timed out), U = 8 with 8 live sequences (1.48 against
+      // 1.39 us/step), one barrier per step (LSTM 1.59 against 1.53).  Its producers store
+      // later in the step on the gate-major chain: first poll after 6 (1.12 -> 1.08 us/step),
+      // 3 on the cell-row chain (0.99-1.00 at 2..4 against 1.04 at 6)
+      r.units = 8;
+      r.cr = sw.cellrows != 0;
+      if (sw.psleep < 0) r.psleep = r.cr ? 3 : 6;
+    } else if (cell == 1) {
+      r.cr = sw.cellrows != 0;
+    } else if (post && sw.nb != 16 && 2 * ((B + 7) / 8) * (H / 16) <= cus) {
+      r.nbl = 8;  // 8 live sequences per group when twice the groups still fit at once (c3
+                  // postnet GRU: 256 instead of 128 workgroups, half the h bytes per step)
+    }
+  }
+  r.wg_per_group = H / r.units;
+  r.threads = r.wg_per_group == 1 ? 256 : 320;
+  r.groups = 2 * ((B + r.nbl - 1) / r.nbl);  // chunks of nbl sequences, two directions each
+  r.groups_per_pass = (cus / r.wg_per_group) & ~1;
+  if (r.groups_per_pass < 2) return r;
+  r.passes = (r.groups + r.groups_per_pass - 1) / r.groups_per_pass;
+  r.first_blocks = rnn_pass_blocks(r, r.passes > 1 ? r.groups_per_pass : r.groups);
+  r.status = FTMI_OK;
+  return r;
+}
+
+// One line per instantiation: the route's template coordinates -> its launcher
+template <auto K>
+int rnn_go(const RnnParams &p, int nblk, int nt, hipStream_t s) {
+  if (int rc = ftmi_resident_ok((const void *)K, nblk, nt, 0)) return rc;
+  hipLaunchKernelGGL(K, dim3(nblk), dim3(nt), 0, s, p);
   FTMI_CHECK_LAUNCH();
   return FTMI_OK;
 }
-
-template <int CELL, int H, int U, int WK, int MODE, bool CST = false, int NBL = NB,
-          bool CR = false>
-int launch_rnn(RnnParams p, int nchunks, int max_blocks, hipStream_t s) {
-  if (NBL != NB) {  // chunks of NBL sequences (the caller counted chunks of NB)
-    nchunks = (p.B + NBL - 1) / NBL;
-    p.ngroups_total = 2 * nchunks;
-  }
-  if (!hx_fits(p, H, (int64_t)NB * H)) return FTMI_E_SHAPE;  // never index past the workspace
-  constexpr int BPG = H / U;
-  int max_groups = (max_blocks / BPG) & ~1;
-  if (max_groups < 2) return FTMI_E_UNSUPPORTED;
-  for (int c0 = 0; c0 < nchunks; c0 += max_groups / 2) {
-    const int nc = (nchunks - c0) < max_groups / 2 ? (nchunks - c0) : max_groups / 2;
-    p.chunk0 = c0;
-    p.ngroups = 2 * nc;
-    if (c0 > 0) {  // the census words are per launch
-      hipError_t e = hipMemsetAsync(p.ws + WS_CENSUS, 0, (WS_FLAGS - WS_CENSUS) * 4, s);
-      if (e != hipSuccess) return (int)e;
-    }
-    // fewer than 8 groups (small batches): pad the grid to BPG workgroups per XCD so that
-    // each group can run inside one XCD (the census picks the layout); FTMI_RNN_PAD=0 off
-    static const int pad_env = [] {
-      const char *v = getenv("FTMI_RNN_PAD");
-      return v ? atoi(v) : 1;
-    }();
-    int nblk = p.ngroups * BPG;
-    if (BPG > 1 && pad_env && p.xcd_local && p.ngroups < 8 && 8 * BPG <= max_blocks)
-      nblk = 8 * BPG;
-    if (int rc = ftmi_resident_ok((const void *)rnn_bidir_kernel<CELL, H, U, WK, MODE, CST, NBL, CR>,
-                                  nblk, BPG == 1 ? 256 : 320, 0))
-      return rc;
-    hipLaunchKernelGGL((rnn_bidir_kernel<CELL, H, U, WK, MODE, CST, NBL, CR>), dim3(nblk),
-                       dim3(BPG == 1 ? 256 : 320), 0, s, p);
-    FTMI_CHECK_LAUNCH();
-  }
-  return FTMI_OK;
-}
+struct RnnKernel {
+  int cell, H, units, wk, mode, cst, nbl, cr, kseg, nbv;
+  int (*go)(const RnnParams &, int, int, hipStream_t);
+};
+#define BIDIR(C, H, U, WK, M, CST, NBL, CR) \
+  {C, H, U, WK, M, CST, NBL, CR, 0, 0, rnn_go<rnn_bidir_kernel<C, H, U, WK, M, CST, NBL, CR>>}
+#define GEMV1(C, H, KSEG, NBV) {C, H, 16, 0, 0, 0, 0, 0, KSEG, NBV, rnn_go<rnn_gemv_kernel<C, H, 16, NBV, KSEG>>}
+#define GEMV(C, H, KSEG) GEMV1(C, H, KSEG, 1), GEMV1(C, H, KSEG, 2), GEMV1(C, H, KSEG, 4)
+const RnnKernel RNN_KERNELS[] = {
+    GEMV(1, 512, 8), GEMV(1, 512, 16), GEMV(0, 256, 8), GEMV(0, 256, 16), GEMV(0, 128, 8), GEMV(0, 64, 8),
+    BIDIR(0, 64, 32, 2, 2, false, NB, false),
+    BIDIR(0, 64, 64, 2, 2, false, NB, false), BIDIR(0, 64, 64, 2, 1, false, NB, false),
+    BIDIR(0, 64, 64, 4, 0, false, NB, false),
+    BIDIR(0, 128, 16, 4, 2, false, NB, false), BIDIR(0, 128, 16, 4, 1, false, NB, false),
+    BIDIR(0, 128, 16, 4, 0, false, NB, false),
+    BIDIR(0, 256, 8, 4, 2, true, NB, true), BIDIR(0, 256, 8, 4, 2, true, NB, false),
+    BIDIR(1, 512, 16, 4, 2, true, NB, true), BIDIR(1, 512, 16, 4, 2, true, NB, false),
+    BIDIR(0, 256, 16, 4, 2, true, 8, false), BIDIR(0, 256, 16, 4, 2, true, NB, false),
+    BIDIR(0, 256, 16, 4, 2, false, NB, false), BIDIR(0, 256, 16, 4, 1, false, NB, false),
+    BIDIR(0, 256, 16, 4, 0, false, NB, false),
+    BIDIR(1, 512, 16, 4, 2, false, NB, false), BIDIR(1, 512, 16, 4, 1, false, NB, false),
+    BIDIR(1, 512, 16, 4, 0, false, NB, false),
+};
+#undef BIDIR
+#undef GEMV
+#undef GEMV1
 
 int device_cu_count() {
   static int cus = 0;
@@ -1225,93 +1325,29 @@ int device_cu_count() {
   return cus;
 }
 
+// the route as the next launch takes it: the switches now, the device's CUs unless given (an
+// unsupported shape is refused before that query, so it leaves no HIP error behind)
+static RnnRoute route_now(int cell, int B, int H, int mma, int cus) {
+  if (cus <= 0) cus = rnn_shape_ok(cell, H) ? device_cu_count() : 1;
+  return rnn_route(cell, B, H, mma & 0xFF, (mma & FTMI_RNN_SPREAD) != 0, cus, read_rnn_switches());
+}
+
 }  // namespace
 
-// B <= GV_MAXB: the exact-fp32 GEMV recurrence (rnn_gemv_kernel), 16 units per workgroup;
-// FTMI_RNN_GEMV=0 keeps the MFMA kernel
-constexpr int GV_MAXB = 4;
-static bool gemv_path(int cell, int B, int H) {
-  const char *v = getenv("FTMI_RNN_GEMV");  // read per call: tests switch it
-  const int env = v ? atoi(v) : 1;
-  return env && B <= GV_MAXB && ((cell == 1 && H == 512) || (cell == 0 && (H == 64 || H == 128 || H == 256)));
-}
-static int xcd_local_env() {  // read per call: tests switch it
-  const char *e = getenv("FTMI_RNN_XCD_LOCAL");
-  return e ? atoi(e) : 1;
+extern "C" int ftmi_rnn_route(int32_t cell, int32_t B, int32_t H, int32_t mma, int32_t cus,
+                              ftmi_rnn_route_t *out) {
+  if (!out || B <= 0 || H <= 0 || cus < 0 || (mma & ~FTMI_RNN_SPREAD) < 0 ||
+      (mma & ~FTMI_RNN_SPREAD) > 2)
+    return FTMI_E_ARG;
+  *out = route_now(cell, B, H, mma, cus);
+  return FTMI_OK;
 }
 
-// hidden units per workgroup of the instance ftmi_rnn_bidir dispatches (see there)
-static int rnn_units(int cell, int H, int mma) {
-  if (cell == 0 && H == 64) {
-    static const int u64 = [] {
-      const char *v = getenv("FTMI_RNN_U64");
-      return v ? atoi(v) : 32;
-    }();
-    return (mma == 2 && u64 == 32) ? 32 : 64;
-  }
-  return 16;
-}
-
-// FTMI_RNN_CSTORE=0 (read per call) keeps the comm wave's h stores: measured at c3, the
-// compute waves' own stores take the postnet GRU 1.315 -> 1.116 us/step, the LSTM 1.55 ->
-// 1.535 (barrier C and the stage read leave the hand-off's critical path)
-static bool cst_enabled() {
-  const char *v = getenv("FTMI_RNN_CSTORE");
-  return !(v && atoi(v) == 0);
-}
-// FTMI_RNN_CELLROWS=0 (read per call: the A/B and tests switch it) keeps the gate-major W_hh
-// rows and the four-byte K-split reduction for the CST LSTM (U = 16) and the U = 8 GRU
-// (rnn_bidir_kernel CR); bit-identical results either way
-static bool cellrows_enabled() {
-  const char *v = getenv("FTMI_RNN_CELLROWS");
-  return !(v && atoi(v) == 0);
-}
-// live sequences per group of a spread f16x3 GRU on rnn_bidir_kernel: 8 when twice the groups
-// still fit the device at once (the c3 postnet GRU: 256 instead of 128 workgroups, half the h
-// bytes per workgroup and step); FTMI_RNN_NB=16 keeps 16 (read per call)
-static int legacy_nbl(int cell, int B, int H, int mma, bool spread, int maxb) {
-  const char *v = getenv("FTMI_RNN_NB");
-  if (!spread || mma != 2 || cell != 0 || H != 256 || !cst_enabled() ||
-      (v && atoi(v) == 16))
-    return NB;
-  return 2 * ((B + 7) / 8) * (H / 16) <= maxb ? 8 : NB;
-}
-
-// The spread postnet GRU (H 256, f16x3, CST) on workgroups of 8 units (rnn_bidir_kernel
-// U = 8) while every group's workgroups fit one per CU (B <= 64 on 256 CUs: 8 groups x 32);
-// FTMI_RNN_U8=0 (read per call: tests switch it) keeps 16 units.  Rejected this round and
-// removed: U = 8 for the LSTM (64 workgroups per group, two per CU — both of the same group
-// under the census layout, so no MFMA time is saved, and five-wave workgroups at 150 VGPRs
-// were not reliably co-resident two per CU: the census timed out), the GRU at U = 8 with 8
-// live sequences (1.48 against 1.39 us/step) and one barrier per step (parity-buffered
-// partials: LSTM 1.59 against 1.53, GRU at U = 8 1.18 against 1.11).
-static bool u8_path(int cell, int B, int H, int mma, bool spread, int maxb) {
-  if (!spread || mma != 2 || !cst_enabled() || cell != 0 || H != 256) return false;
-  const char *v = getenv("FTMI_RNN_U8");
-  if (v && atoi(v) == 0) return false;
-  const int ngroups = 2 * ((B + NB - 1) / NB);
-  return (ngroups < 8 ? 8 : ngroups) * (H / 8) <= maxb;
-}
+extern "C" uint64_t ftmi_rnn_switches_digest(void) { return read_rnn_switches().digest; }
 
 extern "C" int32_t ftmi_rnn_blocks(int32_t cell, int32_t B, int32_t H, int32_t mma) {
-  if (B <= 0 || H <= 0 || H % 16 != 0) return 0;
-  const bool spread = (mma & FTMI_RNN_SPREAD) != 0;
-  mma &= 0xFF;
-  if (gemv_path(cell, B, H)) return (xcd_local_env() ? 8 : 2) * (H / 16);  // launch_gemv
-  if (u8_path(cell, B, H, mma, spread, device_cu_count())) {  // launch_rnn U = 8: one group
-    const int ngroups = 2 * ((B + NB - 1) / NB);                // pass, padded to 8 groups
-    return (ngroups < 8 && xcd_local_env() ? 8 : ngroups) * (H / 8);
-  }
-  const int bpg = H / rnn_units(cell, H, mma);
-  const int maxb = device_cu_count();
-  const int max_groups = (maxb / bpg) & ~1;
-  if (max_groups < 2) return 0;
-  const int nbl = legacy_nbl(cell, B, H, mma, spread, maxb);
-  const int nchunks = (B + nbl - 1) / nbl;
-  const int ngroups = 2 * (nchunks < max_groups / 2 ? nchunks : max_groups / 2);
-  int nblk = ngroups * bpg;
-  if (bpg > 1 && ngroups < 8 && 8 * bpg <= maxb) nblk = 8 * bpg;  // launch_rnn's padding
-  return nblk;
+  const RnnRoute r = route_now(cell, B, H, mma, 0);
+  return r.status == FTMI_OK ? r.first_blocks : 0;
 }
 
 extern "C" int64_t ftmi_rnn_workspace_bytes(int32_t B, int32_t H, int32_t cell) {
@@ -1334,11 +1370,10 @@ extern "C" int64_t ftmi_rnn_error_offset(int32_t B) {
 }
 
 // the launch set-up of ftmi_rnn_bidir: clears the workspace (control words and the exchange buffer) and fills the common parameters
-static int rnn_setup(RnnParams &p, int B, int T, int H, int cell, const float *w_hh,
-                     const float *b_hh, const int32_t *lengths, float pad_value, float *y,
-                     int64_t y_stride, uint32_t *status, void *sync, hipStream_t s,
-                     int &nchunks) {
-  nchunks = (B + NB - 1) / NB;
+static int rnn_setup(RnnParams &p, const RnnRoute &r, int B, int T, int H, int cell,
+                     const float *w_hh, const float *b_hh, const int32_t *lengths,
+                     float pad_value, float *y, int64_t y_stride, uint32_t *status, void *sync,
+                     hipStream_t s) {
   const int64_t ctl = ctl_bytes(ws_chunks(B));
   const int64_t wsb = ftmi_rnn_workspace_bytes(B, H, cell);
   hipError_t e = hipMemsetAsync(sync, 0, (size_t)wsb, s);
@@ -1351,8 +1386,9 @@ static int rnn_setup(RnnParams &p, int B, int T, int H, int cell, const float *w
   p.pad_value = pad_value;
   p.B = B;
   p.T = T;
-  p.ngroups_total = 2 * nchunks;
-  p.xcd_local = xcd_local_env();
+  p.ngroups_total = r.groups;
+  p.xcd_local = r.xcd_local;
+  p.psleep = r.psleep;
   p.ws = (unsigned *)sync;
   p.hx = (float *)((char *)sync + ctl);
   p.status = status;
@@ -1364,26 +1400,7 @@ static int rnn_setup(RnnParams &p, int B, int T, int H, int cell, const float *w
   }();
   p.diag = diag_env;
 #endif
-  // s_sleep(1) count before a step's first h poll (rnn_bidir_kernel): the first poll then
-  // lands after the producers' stores instead of a round trip before them.  Interleaved A/B
-  // at c3 (tools/rnn_env_ab.py, two boxes): 3 -> LSTM 1.55 -> 1.52-1.54, postnet GRU 1.32 ->
-  // 1.27 us/step; 6 made the LSTM slower again (1.58-1.61)
-  // (-1 = unset: 3, and 6 for the spread postnet GRU on 8-unit workgroups — its producers
-  // store later in the step: 1.12-1.13 -> 1.08 us/step at c3, round 5, profiles/r5_rnn_diag.txt)
-  static const int psleep_env = [] {
-    const char *v = getenv("FTMI_RNN_PSLEEP");
-    return v ? atoi(v) : -1;
-  }();
-  p.psleep = psleep_env < 0 ? 3 : psleep_env;
   return FTMI_OK;
-}
-
-// first-poll delay of the U = 8 spread GRU (see rnn_setup): 6 on the gate-major chain, 3 on
-// the cell-row chain, whose producers store earlier in the step (c3, two interleaved rounds of
-// tools/rnn_diag.py: 0.99-1.00 at 2..4 against 1.04 us/step at 6)
-static int u8_psleep() {
-  const char *v = getenv("FTMI_RNN_PSLEEP");
-  return v ? atoi(v) : (cellrows_enabled() ? 3 : 6);
 }
 
 extern "C" int ftmi_rnn_bidir(int32_t cell, int32_t B, int32_t T, int32_t H, const float *xp,
@@ -1394,83 +1411,43 @@ extern "C" int ftmi_rnn_bidir(int32_t cell, int32_t B, int32_t T, int32_t H, con
                               ftmi_stream_t stream) {
   if (!xp || !w_hh || !y || !sync) return FTMI_E_ARG;
   if (B <= 0 || T <= 0 || H <= 0 || T_src <= 0) return FTMI_E_ARG;
-  const bool spread = (mma & FTMI_RNN_SPREAD) != 0;
-  mma &= ~FTMI_RNN_SPREAD;
-  if (mma < 0 || mma > 2) return FTMI_E_ARG;
+  if ((mma & ~FTMI_RNN_SPREAD) < 0 || (mma & ~FTMI_RNN_SPREAD) > 2) return FTMI_E_ARG;
   if (cell == 0 && !b_hh) return FTMI_E_ARG;
   if (index && !xp_zero) return FTMI_E_ARG;
   if (!index && T_src != T) return FTMI_E_SHAPE;
   if (!ftmi_aligned16(w_hh) || !ftmi_aligned16(sync)) return FTMI_E_ALIGN;
   if (!ftmi_aligned16(y) || (y_stride & 3)) return FTMI_E_ALIGN;  // float4 row stores
-  // the kernel forms below: GRU H 64 / 128 / 256, LSTM H 512 — refused before any HIP call
-  // (the workspace memset), so an unsupported shape leaves no HIP error behind
-  if (cell == 1 ? H != 512 : (cell != 0 || (H != 64 && H != 128 && H != 256)))
-    return FTMI_E_UNSUPPORTED;
+  // refused before any HIP call (the workspace memset): no HIP error is left behind
+  const RnnRoute r = route_now(cell, B, H, mma, 0);
+  if (r.status != FTMI_OK) return r.status;
   hipStream_t s = ftmi_hs(stream);
   RnnParams p = {};
-  int nchunks = 0;
-  const int rc = rnn_setup(p, B, T, H, cell, w_hh, b_hh, lengths, pad_value, y, y_stride,
-                           status, sync, s, nchunks);
+  const int rc = rnn_setup(p, r, B, T, H, cell, w_hh, b_hh, lengths, pad_value, y, y_stride,
+                           status, sync, s);
   if (rc != FTMI_OK) return rc;
   p.xp = xp;
   p.xp_stride = xp_stride;
   p.T_src = T_src;
   p.index = index;
   p.xp_zero = xp_zero;
-  const int maxb = device_cu_count();
-  // small batches: exact fp32 GEMV recurrence (any mma: it is exact)
-  if (gemv_path(cell, B, H)) {
-    // H = 512 / 256: 16 k-segments per row (512 / 384 threads, half the FMA chain per thread):
-    // c2 LSTM 1.26 -> 1.17-1.18, postnet GRU 1.01 -> 0.96-0.97 us/step (tools/rnn_diag.py,
-    // two interleaved rounds; 32 segments: 1.32-1.34 / 1.07-1.08).  FTMI_RNN_GEMV_KSEG=8 (read
-    // per call) keeps 8.
-    const char *kv = getenv("FTMI_RNN_GEMV_KSEG");
-    const bool k8 = kv && atoi(kv) == 8;
-    if (cell == 1) return k8 ? launch_gemv<1, 512, 16>(p, maxb, s) : launch_gemv<1, 512, 16, 16>(p, maxb, s);
-    if (H == 256) return k8 ? launch_gemv<0, 256, 16>(p, maxb, s) : launch_gemv<0, 256, 16, 16>(p, maxb, s);
-    if (H == 128) return launch_gemv<0, 128, 16>(p, maxb, s);
-    return launch_gemv<0, 64, 16>(p, maxb, s);
-  }
-#define FTMI_RNN_MODES(CELL_, H_, U_, WKX_, WKF_)                                   \
-  switch (mma) {                                                                    \
-    case 2: return launch_rnn<CELL_, H_, U_, WKX_, 2>(p, nchunks, maxb, s);          \
-    case 1: return launch_rnn<CELL_, H_, U_, WKX_, 1>(p, nchunks, maxb, s);          \
-    default: return launch_rnn<CELL_, H_, U_, WKF_, 0>(p, nchunks, maxb, s);         \
-  }
-  // H = 64 on the f16x3 path: 32 units per workgroup (2 per group, h exchanged through L2)
-  // 1.19 us/step against 1.45 for one workgroup per group (h in LDS) at B = 64;
-  // FTMI_RNN_U64=64 selects the single-workgroup form
-  if (cell == 0 && H == 64) {
-    if (rnn_units(cell, H, mma) == 32) return launch_rnn<0, 64, 32, 2, 2>(p, nchunks, maxb, s);
-    FTMI_RNN_MODES(0, 64, 64, 2, 4)
-  }
-  // H = 128: 16 units per workgroup (8 workgroups per group): 1.04 us/step against 2.33 with
-  // 64 units (2 workgroups) at B = 64 — the per-step cell and MFMA work of a workgroup
-  // shrinks 4x for one more hop in the exchange
-  if (cell == 0 && H == 128) FTMI_RNN_MODES(0, 128, 16, 4, 4)
-  // H = 256 / 512: 16 units per workgroup (32 units measured 1.84 against 1.19 us/step for
-  // the H = 256 GRU; the LSTM's W_hh slice does not fit the VGPRs at 32 units)
-  // f16x3, 16 units per workgroup: the compute waves store their own h (CST) and a spread
-  // GRU runs 8 live sequences per group (legacy_nbl).  H = 128 keeps the form above (it
-  // returned before this block since round 3; legacy_nbl agrees, so ftmi_rnn_blocks reports
-  // the launch's real workgroup count)
-  if (mma == 2 && cst_enabled() && ((cell == 1 && H == 512) || (cell == 0 && H == 256))) {
-    const bool nb8 = legacy_nbl(cell, B, H, mma, spread, maxb) == 8;
-    if (u8_path(cell, B, H, mma, spread, maxb)) {
-      p.psleep = u8_psleep();
-      return cellrows_enabled() ? launch_rnn<0, 256, 8, 4, 2, true, NB, true>(p, nchunks, maxb, s)
-                                : launch_rnn<0, 256, 8, 4, 2, true>(p, nchunks, maxb, s);
+  if (!hx_fits(p, H, (int64_t)NB * H)) return FTMI_E_SHAPE;  // never index past the workspace
+  const RnnKernel *k = nullptr;
+  for (const RnnKernel &e : RNN_KERNELS)
+    if (e.cell == r.cell && e.H == r.H && e.units == r.units && e.wk == r.wk &&
+        e.mode == r.mode && e.cst == r.cst && e.nbl == r.nbl && e.cr == r.cr &&
+        e.kseg == r.kseg && e.nbv == r.nbv)
+      k = &e;
+  if (!k) return FTMI_E_UNSUPPORTED;
+  for (int g0 = 0; g0 < r.groups; g0 += r.groups_per_pass) {
+    p.chunk0 = g0 / 2;
+    p.ngroups = r.groups - g0 < r.groups_per_pass ? r.groups - g0 : r.groups_per_pass;
+    if (g0 > 0) {  // the census words are per launch
+      hipError_t e = hipMemsetAsync(p.ws + WS_CENSUS, 0, (WS_FLAGS - WS_CENSUS) * 4, s);
+      if (e != hipSuccess) return (int)e;
     }
-    if (cell == 1)
-      return cellrows_enabled() ? launch_rnn<1, 512, 16, 4, 2, true, NB, true>(p, nchunks, maxb, s)
-                                : launch_rnn<1, 512, 16, 4, 2, true>(p, nchunks, maxb, s);
-    return nb8 ? launch_rnn<0, 256, 16, 4, 2, true, 8>(p, nchunks, maxb, s)
-               : launch_rnn<0, 256, 16, 4, 2, true>(p, nchunks, maxb, s);
+    if (int rc = k->go(p, rnn_pass_blocks(r, p.ngroups), r.threads, s)) return rc;
   }
-  if (cell == 0 && H == 256) FTMI_RNN_MODES(0, 256, 16, 4, 4)
-  if (cell == 1 && H == 512) FTMI_RNN_MODES(1, 512, 16, 4, 4)
-#undef FTMI_RNN_MODES
-  return FTMI_E_UNSUPPORTED;
+  return FTMI_OK;
 }
 
 #ifdef FTMI_RNN_STAMPS

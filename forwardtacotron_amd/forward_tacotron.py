@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import chain, ops
+from . import _lib, chain, ops
 from .common_layers import (CBHG, BatchNormConv, BiRNN, Conv1dParams, LengthRegulator,
                             LinearParams, Packed, pack_conv)
 from .text.symbols import phonemes
@@ -303,7 +303,8 @@ class ForwardTacotron(nn.Module):
             cache[device] = [torch.cuda.Stream(device=device), torch.cuda.Stream(device=device),
                              torch.cuda.Stream(device=device, priority=prio)]
         fits = self.__dict__.setdefault('_ftmi_concurrent', {})
-        key = (device, B, T, ops.RNN_MMA, bool(ops._FORCED), os.environ.get('FTMI_HS_SPREAD', '1'))
+        key = (device, B, T, ops.RNN_MMA, bool(ops._FORCED), os.environ.get('FTMI_HS_SPREAD', '1'),
+               _lib.load().ftmi_rnn_switches_digest())  # ops.rnn_blocks reads those switches
         if key not in fits:
             preds = (self.dur_pred.rnn, self.pitch_pred.rnn, self.energy_pred.rnn)
             need = sum(ops.rnn_blocks(r.cell, B, r.hidden) for r in preds)

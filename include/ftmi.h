@@ -90,7 +90,8 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * ftmi_nonzero_moments, ftmi_normalize_nonzero; ftmi_embed_bank; ftmi_l1_loss,
  * ftmi_cross_entropy, ftmi_mol_loss and their *_workspace_bytes; ftmi_run_chain;
  * 21: ftmi_gemm_route, ftmi_conv1d_route, ftmi_conv_bank_route, ftmi_highway_route,
- * ftmi_gemm_switches_digest; no existing signature changed). */
+ * ftmi_gemm_switches_digest; no existing signature changed;
+ * 22: ftmi_rnn_route, ftmi_rnn_switches_digest; no existing signature changed). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -414,6 +415,45 @@ int64_t ftmi_rnn_error_offset(int32_t B);
  * several streams must not exceed the CU count together (the host serialises them
  * otherwise).  0 for an unsupported shape. */
 int32_t ftmi_rnn_blocks(int32_t cell, int32_t B, int32_t H, int32_t mma);
+/* ABI 22: everything ftmi_rnn_bidir(cell, B, ., H, ..., mma) decides before it launches, from
+ * one host function that reads its switches in the environment on every call (FTMI_RNN_GEMV,
+ * FTMI_RNN_GEMV_KSEG, FTMI_RNN_XCD_LOCAL, FTMI_RNN_PAD, FTMI_RNN_U64, FTMI_RNN_CSTORE,
+ * FTMI_RNN_CELLROWS, FTMI_RNN_NB, FTMI_RNN_U8, FTMI_RNN_PSLEEP).  ftmi_rnn_route runs it
+ * without a launch, a device write or a pointer; ftmi_rnn_blocks is its first_blocks (0 when
+ * status is not FTMI_OK).  mma may carry FTMI_RNN_SPREAD; cus: the CUs to plan for, 0 = the
+ * current device's.  FTMI_E_ARG for a NULL out, B or H <= 0, cus < 0, or an mma that
+ * ftmi_rnn_bidir refuses. */
+enum { FTMI_RNN_KERNEL_NONE = 0, FTMI_RNN_KERNEL_GEMV, /* rnn_gemv_kernel<cell, H, units, nbv, kseg> */
+       FTMI_RNN_KERNEL_BIDIR /* rnn_bidir_kernel<cell, H, units, wk, mode, cst, nbl, cr> */ };
+typedef struct ftmi_rnn_route {
+  int32_t status;          /* FTMI_OK, or FTMI_E_UNSUPPORTED as ftmi_rnn_bidir would return */
+  int32_t kernel;          /* FTMI_RNN_KERNEL_* */
+  int32_t cell;
+  int32_t H;
+  int32_t units;           /* hidden units per workgroup */
+  int32_t wk;              /* BIDIR: K-split waves */
+  int32_t mode;            /* BIDIR: the matrix path (FTMI_MMA_*) */
+  int32_t cst;             /* BIDIR: the compute waves store h */
+  int32_t nbl;             /* BIDIR: live sequences per group */
+  int32_t cr;              /* BIDIR: cell-row W_hh order */
+  int32_t kseg;            /* GEMV: k-segments per row */
+  int32_t nbv;             /* GEMV: sequences per workgroup */
+  int32_t threads;         /* per workgroup */
+  int32_t wg_per_group;    /* workgroups that exchange h each step: H / units */
+  int32_t groups;          /* over all passes: two directions per chunk of sequences */
+  int32_t groups_per_pass; /* most groups one launch holds on `cus` CUs */
+  int32_t passes;          /* launches */
+  int32_t first_blocks;    /* workgroups of the first launch, padding included */
+  int32_t xcd_local;       /* FTMI_RNN_XCD_LOCAL as the kernel receives it */
+  int32_t pad;             /* fewer than 8 groups are padded to one per XCD (if xcd_local) */
+  int32_t psleep;          /* s_sleep(1) count before a step's first h poll */
+  int32_t cus;             /* the CU count the grid was planned for */
+} ftmi_rnn_route_t;
+int ftmi_rnn_route(int32_t cell, int32_t B, int32_t H, int32_t mma, int32_t cus,
+                   ftmi_rnn_route_t *out);
+/* 64-bit digest of those switches as the next call would read them: equal digests, equal
+ * routes for equal arguments. */
+uint64_t ftmi_rnn_switches_digest(void);
 /* Test / diagnostic hook: bound of every recurrence spin (polls per wait) for launches
  * issued after the call; 0 restores the default (2^22).  Returns the previous bound. */
 uint32_t ftmi_set_rnn_spin_limit(uint32_t limit);

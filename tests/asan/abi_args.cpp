@@ -107,6 +107,17 @@ int main() {
                         nullptr, a, nullptr), FTMI_E_ARG);
   EXPECT(ftmi_rnn_bidir(0, 1, 1, 64, a, 192, 1, nullptr, nullptr, mis, a, nullptr, 0.f, a, 128, 2,
                         nullptr, a, nullptr), FTMI_E_ALIGN);
+  // the recurrence's route query (host only: the environment scan and rnn_route())
+  ftmi_rnn_route_t rr;
+  EXPECT(ftmi_rnn_route(0, 64, 256, 2, 256, nullptr), FTMI_E_ARG);
+  EXPECT(ftmi_rnn_route(0, 0, 256, 2, 256, &rr), FTMI_E_ARG);
+  EXPECT(ftmi_rnn_route(0, 64, 256, 3, 256, &rr), FTMI_E_ARG);
+  EXPECT(ftmi_rnn_route(0, 64, 256, 2 | FTMI_RNN_SPREAD, 256, &rr), FTMI_OK);
+  EXPECT(rr.status, FTMI_OK);
+  EXPECT(rr.first_blocks, 256);
+  EXPECT(ftmi_rnn_route(0, 64, 96, 2, 256, &rr), FTMI_OK);
+  EXPECT(rr.status, FTMI_E_UNSUPPORTED);
+  EXPECT(ftmi_rnn_switches_digest() == ftmi_rnn_switches_digest(), 1);
   EXPECT(ftmi_attention(nullptr, 0, 1, 1, 1, 64, 0, 64, 128, nullptr, 1.f, nullptr, 0, 2, nullptr,
                         nullptr, 0, nullptr), FTMI_E_ARG);
   EXPECT(ftmi_attention(a, 192, 1, 1, 1, 96, 0, 96, 192, nullptr, 1.f, a, 96, 2, nullptr, nullptr,

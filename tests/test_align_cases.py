@@ -139,7 +139,7 @@ def test_header_and_binding_agree():
         res, args = _lib.SIGNATURES[name]
         assert args == want, name
         assert res == ctype[ret], name
-    assert _lib.ABI_VERSION == 21
+    assert _lib.ABI_VERSION == 22
     lib = _lib.load()
     assert all(hasattr(lib, n) for n in ALIGN_FUNCS)
 

@@ -91,7 +91,7 @@ def test_workspace_queries():
 
 
 def test_abi_number_unchanged():
-    assert _lib.ABI_VERSION == 21 and _lib.load().ftmi_abi_version() == 21
+    assert _lib.ABI_VERSION == 22 and _lib.load().ftmi_abi_version() == 22
 
 
 def test_ops_refuse_cpu_tensors_and_wrong_dtypes():

@@ -770,6 +770,43 @@ def test_rnn_f16x3_kernels(cell, H, B, T, variant, rng, monkeypatch):
     close(host(m.forward_cl(dev(x))), ref, rtol=1e-4, atol=1e-5)
 
 
+# (H, B, T, spread, switches, rnn_bidir_kernel<0, H, U, WK, MODE, CST, NBL, CR>, workgroups)
+PER_CALL_CASES = [
+    # one workgroup per group, h through LDS (B <= 4 takes the GEMV kernel: switched off)
+    pytest.param(64, 3, 40, False, {'U64': '64', 'GEMV': '0'}, (64, 2, 2, False, 16, False), 2, id='u64'),
+    # the unpadded one-chunk grid: 2 groups of 16 workgroups instead of one group per XCD
+    pytest.param(256, 1, 31, False, {'GEMV': '0', 'PAD': '0'}, (16, 4, 2, True, 16, False), 32, id='pad0'),
+    # the spread GRU on 16 units and 16 live sequences per group
+    pytest.param(256, 17, 9, True, {'NB': '16', 'U8': '0'}, (16, 4, 2, True, 16, False), 128, id='nb16'),
+]
+
+
+@pytest.mark.parametrize('H,B,T,spread,switches,kernel,blocks', PER_CALL_CASES)
+def test_gru_forms_behind_per_call_switches(H, B, T, spread, switches, kernel, blocks, rng, monkeypatch):
+    """The f16x3 GRU forms that FTMI_RNN_U64 / FTMI_RNN_PAD select (switches the library kept
+    from its first call before ABI 22, so no test could reach them) and the spread 16-unit,
+    16-sequence form: the route names the kernel, ftmi_rnn_blocks reports its grid, and the
+    result meets the numpy oracle."""
+    import ctypes
+    from forwardtacotron_amd import _lib, ops
+    monkeypatch.setattr(ops, 'RNN_MMA', 2)
+    for name in ('GEMV', 'GEMV_KSEG', 'XCD_LOCAL', 'PAD', 'U64', 'CSTORE', 'CELLROWS', 'NB', 'U8', 'PSLEEP'):
+        monkeypatch.delenv('FTMI_RNN_' + name, raising=False)
+    for name, value in switches.items():
+        monkeypatch.setenv('FTMI_RNN_' + name, value)
+    mma = 2 | (ops.RNN_SPREAD if spread else 0)
+    r = _lib.RnnRoute()
+    assert _lib.load().ftmi_rnn_route(0, B, H, mma, 0, ctypes.byref(r)) == 0
+    assert (r.status, r.kernel) == (0, _lib.RNN_KERNEL_BIDIR)
+    assert (r.units, r.wk, r.mode, bool(r.cst), r.nbl, bool(r.cr)) == kernel
+    assert ops.rnn_blocks(0, B, H, mma) == r.first_blocks == blocks and r.passes == 1
+    m, sd = _rnn_module('gru', 256, H, rng)
+    m.spread = spread
+    x = rng.normal(0, 1, (B, T, 256)).astype(np.float32)
+    ref = O.gru_bidir(sd, 'r', x, np.float32)
+    close(host(m.forward_cl(dev(x))), ref, rtol=1e-4, atol=1e-5)
+
+
 GEMV_CASES = [('lstm', 512, 1, 37), ('lstm', 512, 2, 20), ('lstm', 512, 4, 15), ('gru', 256, 1, 50),
               ('gru', 256, 3, 21), ('gru', 128, 1, 33), ('gru', 128, 4, 17), ('gru', 64, 1, 40),
               ('gru', 64, 2, 25)]

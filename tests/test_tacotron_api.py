@@ -96,7 +96,7 @@ def test_binding_struct_mirrors_header():
     names = [n.split()[-1].lstrip('*') for decl in body.split(';') if decl.strip()
              for n in decl.split(',')]
     assert names == [f[0] for f in _lib.TacoArgs._fields_]
-    assert _lib.ABI_VERSION == 21
+    assert _lib.ABI_VERSION == 22
     from forwardtacotron_amd import ops
     lim = dict(re.findall(r'(FTMI_TACO_MAX_[A-Z]+) = (\d+)', text))
     assert (ops.TACO_MAX_TOKENS, ops.TACO_MAX_BATCH) == (int(lim['FTMI_TACO_MAX_TOKENS']), int(lim['FTMI_TACO_MAX_BATCH']))
