@@ -4,7 +4,8 @@ replaces (FTMI_RNN_CELLROWS=0): the K-split partials are added in the same order
 be bit-identical — every frame of both directions, which includes the final hidden states
 (y[:, len - 1, :H] forward, y[:, 0, H:] reverse; the cell state is not exposed, but every
 h_t = o * tanh(c_t) is).  The gate-major form itself is held to the numpy oracle by
-test_gpu_kernels.py and the model tests.
+test_gpu_kernels.py and the model tests; test_gpu_rnn_cases.py holds both layouts to float64
+with lengths / index, T < 3 and off the unit value scale (a mistake both layouts share).
 
 Shapes: the LSTM (H 512, 16 units per workgroup) at B = 5 (one ragged chunk, past the GEMV
 kernel's B <= 4), 16 (one full chunk), 17 (a ragged second chunk), 64 (four chunks: one
