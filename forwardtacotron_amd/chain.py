@@ -24,7 +24,8 @@ A module keeps at most MAX_PLANS plans (least recently used dropped).  Recording
 per-op pass plus the rewrite (tools/chain_build_cost.py measures it), so a caller whose
 shapes never repeat pays that on top of every call: FTMI_CHAIN=0 is the setting for it.
 A plan's op and base arrays are patched in place per call: one host thread per module at a
-time (as everywhere in this package: the packs and graph caches are not locked either).
+time (as everywhere in this package: neither the packs (common_layers.cached_pack) nor the
+captured phases (phase_graph) are locked either).
 
 FTMI_CHAIN=0 (or chain.CHAIN = False) keeps the per-op path: per-kernel profiling, A/B.
 """
@@ -38,6 +39,7 @@ import torch
 
 from . import _lib, ops, probe
 from ._lib import ChainBase, ChainOp, FtmiError
+from .common_layers import cached_pack
 
 CHAIN = os.environ.get('FTMI_CHAIN', '1') != '0'
 BUILDS = 0  # plans built so far (tests count them)
@@ -254,13 +256,10 @@ def policy_key():
             _lib.load().ftmi_gemm_switches_digest())
 
 
-def _plans(mod, pack_key):
+def _plans(mod):
     """The module's plans of its current weights: they live on the module next to its packs
     and are dropped with them (load_state_dict, .to, in-place updates change the pack key)."""
-    cache = mod.__dict__.get('_ftmi_chain')
-    if cache is None or cache[0] != pack_key:
-        cache = mod.__dict__['_ftmi_chain'] = (pack_key, {})
-    return cache[1]
+    return cached_pack(mod, '_ftmi_chain', dict)
 
 
 def _lookup(plans, key):
@@ -288,7 +287,7 @@ def _predictor_key(mod, ids):
 def cached_plan(mod, ids: torch.Tensor) -> Optional[Plan]:
     """The plan a SeriesPredictor call with these ids would run now, or None if it would
     record one."""
-    return _plans(mod, mod._pack_key()).get(_predictor_key(mod, _ids(ids)))
+    return _plans(mod).get(_predictor_key(mod, _ids(ids)))
 
 
 def series_predictor(mod, x: torch.Tensor, alpha: float) -> torch.Tensor:
@@ -296,7 +295,7 @@ def series_predictor(mod, x: torch.Tensor, alpha: float) -> torch.Tensor:
     (with their split-K finishes), the GRU input projection, the recurrence and the head."""
     ops._dev(x, mod.embedding.weight)
     ids = _ids(x)
-    plans, key = _plans(mod, mod._pack_key()), _predictor_key(mod, ids)
+    plans, key = _plans(mod), _predictor_key(mod, ids)
     plan = _lookup(plans, key)
     if plan is None:
         # the packs first: building one launches its own (unrecorded) split kernels

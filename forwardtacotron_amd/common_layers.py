@@ -21,6 +21,58 @@ import torch.nn as nn
 from . import ops
 
 # --------------------------------------------------------------------------------------
+# packed-weight cache: rebuilt whenever a parameter / buffer changes (load_state_dict, .to)
+
+def weights_key(module: nn.Module):
+    """(data_ptr, _version) of every parameter and buffer under `module`."""
+    # The (owner dict, name, tensor) list is cached: walking the module tree costs ~10 us
+    # per call, which is host time on the launch path.  A parameter / buffer REPLACED in
+    # any submodule (owner dict no longer holds the same object) rebuilds the list; an
+    # in-place change (load_state_dict, .to, .copy_) changes data_ptr or _version.
+    refs = module.__dict__.get('_ftmi_refs')
+    if refs is None or any(d.get(n) is not t for d, n, t in refs):
+        refs = [(d, n, t) for m in module.modules() for d in (m._parameters, m._buffers)
+                for n, t in d.items() if t is not None]
+        module.__dict__['_ftmi_refs'] = refs
+    return tuple((t.data_ptr(), t._version) for _, _, t in refs)
+
+
+def cached_pack(module: nn.Module, slot: str, build, extra=None):
+    """`build()` (run under no_grad) of the module's current weights, kept in
+    module.__dict__[slot] as (key, value) and rebuilt when weights_key(module) or `extra`
+    (whatever else the value was made from) changes.  Every pack, table and plan cache of
+    the package is one call of this; the slots written are noted on the module, so
+    held_packs finds them all."""
+    key = (weights_key(module), extra)
+    cache = module.__dict__.get(slot)
+    if cache is None or cache[0] != key:
+        with torch.no_grad():
+            cache = (key, build())
+        module.__dict__[slot] = cache
+        module.__dict__.setdefault('_ftmi_slots', set()).add(slot)
+    return cache[1]
+
+
+def held_packs(model: nn.Module) -> list:
+    """Every value cached_pack holds on `model` or a submodule: what a captured graph of
+    the model's kernels may read, and so must keep alive."""
+    return [m.__dict__[s][1] for m in model.modules() for s in m.__dict__.get('_ftmi_slots', ())]
+
+
+class Packed(nn.Module):
+    """Base class: caches kernel-layout weights, keyed by the identity/version of params."""
+
+    def _pack_key(self):
+        return weights_key(self)
+
+    def packed_weights(self):
+        return cached_pack(self, '_ftmi_pack', self._pack)
+
+    def _pack(self):  # pragma: no cover - abstract
+        raise NotImplementedError
+
+
+# --------------------------------------------------------------------------------------
 # parameter holders (same tensors as nn.Conv1d / nn.BatchNorm1d / nn.Linear / nn.GRU / nn.LSTM)
 
 
@@ -63,8 +115,9 @@ class BatchNorm1dParams(nn.Module):
         return scale.detach().float().contiguous(), shift.detach().float().contiguous()
 
 
-class LinearParams(nn.Module):
-    """Parameters of nn.Linear(fin, fout, bias=...)."""
+class LinearParams(Packed):
+    """Parameters of nn.Linear(fin, fout, bias=...); packed_weights(): (weight, bias or
+    None, pre-split weight) for ops.conv1d."""
 
     def __init__(self, fin: int, fout: int, bias: bool = True) -> None:
         super().__init__()
@@ -76,18 +129,10 @@ class LinearParams(nn.Module):
         if self.bias is not None:
             _uniform_(self.bias, b)
 
-    def packed_weights(self):
-        """(weight, bias or None, pre-split weight) for ops.conv1d, cached on the parameter
-        identity / version like Packed."""
-        key = tuple((t.data_ptr(), t._version, t.device) for t in self.parameters())
-        cache = self.__dict__.get('_ftmi_pack')
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                w = self.weight.detach().contiguous()
-                b = None if self.bias is None else self.bias.detach().contiguous()
-                cache = (key, (w, b, presplit(w)))
-            self.__dict__['_ftmi_pack'] = cache
-        return cache[1]
+    def _pack(self):
+        w = self.weight.detach().contiguous()
+        b = None if self.bias is None else self.bias.detach().contiguous()
+        return w, b, presplit(w)
 
 
 def pack_conv(w: torch.Tensor) -> torch.Tensor:
@@ -99,37 +144,6 @@ def presplit(w: torch.Tensor):
     """Pre-split operand of a packed weight for the default matrix path (ops.MMA): f16
     planes (f16x3), bf16 pieces (bf16x6) or None (fp32)."""
     return ops.presplit_for(w)
-
-
-# --------------------------------------------------------------------------------------
-# packed-weight cache: rebuilt whenever a parameter / buffer changes (load_state_dict, .to)
-
-class Packed(nn.Module):
-    """Base class: caches kernel-layout weights, keyed by the identity/version of params."""
-
-    def _pack_key(self):
-        # The (owner dict, name, tensor) list is cached: walking the module tree costs ~10 us
-        # per call, which is host time on the launch path.  A parameter / buffer REPLACED in
-        # any submodule (owner dict no longer holds the same object) rebuilds the list; an
-        # in-place change (load_state_dict, .to, .copy_) changes data_ptr or _version.
-        refs = self.__dict__.get('_ftmi_refs')
-        if refs is None or any(d.get(n) is not t for d, n, t in refs):
-            refs = [(d, n, t) for m in self.modules() for d in (m._parameters, m._buffers)
-                    for n, t in d.items() if t is not None]
-            self.__dict__['_ftmi_refs'] = refs
-        return tuple((t.data_ptr(), t._version) for _, _, t in refs)
-
-    def packed_weights(self):
-        key = self._pack_key()
-        cache = self.__dict__.get('_ftmi_pack')
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                cache = (key, self._pack())
-            self.__dict__['_ftmi_pack'] = cache
-        return cache[1]
-
-    def _pack(self):  # pragma: no cover - abstract
-        raise NotImplementedError
 
 
 # --------------------------------------------------------------------------------------
@@ -313,15 +327,9 @@ class CBHG(Packed):
         [channels] fp32, built in fp64), cached like every pack: keyed on this module's
         parameters and the embedding weight's identity / version / device, so it is rebuilt
         after load_state_dict, .to or an in-place change of either."""
-        key = (self._pack_key(), embedding_weight.data_ptr(), embedding_weight._version,
-               embedding_weight.device)
-        cache = self.__dict__.get('_ftmi_embed_table')
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                cache = (key, ops.embed_bank_table(
-                    embedding_weight, [c.conv.weight for c in self.conv1d_bank]))
-            self.__dict__['_ftmi_embed_table'] = cache
-        return cache[1]
+        w = embedding_weight
+        return cached_pack(self, '_ftmi_embed_table', lambda: ops.embed_bank_table(
+            w, [c.conv.weight for c in self.conv1d_bank]), (w.data_ptr(), w._version, w.device))
 
     def forward_ids(self, x_ids: torch.Tensor, embedding_weight: torch.Tensor) -> torch.Tensor:
         """forward_cl(embedding(x_ids)): (B, T) ids -> (B, T, 2*channels).  From
@@ -364,19 +372,15 @@ class CBHG(Packed):
     def _stack_pack(self):
         """Fragment-major f16x3 blocks of pre_highway, the highways' w12 and the GRU's W_ih
         (the operands of ops.highway_stack), cached like every pack (rebuilt with the params)."""
-        key = self._pack_key()
-        cache = self.__dict__.get('_ftmi_stack')
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                w_pre = self.packed_weights()[3]
-                hw = [m.packed_weights() for m in self.highways]
-                w_ih, b_in = self.rnn.packed_weights()[:2]
-                f16 = ops.split_weights_f16
-                cache = (key, (f16(w_pre, frag=True), [f16(p[0], frag=True) for p in hw],
-                               [p[1] for p in hw], [p[2] for p in hw], f16(w_ih, frag=True),
-                               b_in, w_ih.size(0)))
-            self.__dict__['_ftmi_stack'] = cache
-        return cache[1]
+        def build():
+            w_pre = self.packed_weights()[3]
+            hw = [m.packed_weights() for m in self.highways]
+            w_ih, b_in = self.rnn.packed_weights()[:2]
+            f16 = ops.split_weights_f16
+            return (f16(w_pre, frag=True), [f16(p[0], frag=True) for p in hw],
+                    [p[1] for p in hw], [p[2] for p in hw], f16(w_ih, frag=True), b_in,
+                    w_ih.size(0))
+        return cached_pack(self, '_ftmi_stack', build)
 
     def spread_blocks(self, M: int) -> int:
         """Workgroups the spread CBHG tail would hold resident for M rows (0: the fused

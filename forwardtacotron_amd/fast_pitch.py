@@ -23,18 +23,19 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
-from .common_layers import Conv1dParams, LengthRegulator, LinearParams, Packed, pack_conv, presplit
-from .forward_tacotron import Embedding, _graphable, _identity
+from . import ops, phase_graph
+from .common_layers import (Conv1dParams, LengthRegulator, LinearParams, Packed, cached_pack,
+                            pack_conv, presplit)
+from .forward_tacotron import Embedding
+from .phase_graph import _identity
+from .text.symbols import phonemes
 
 # generate() replays the phoneme phase (three predictors, the prenet, the duration counts:
 # ~160 launches over four streams) as a HIP graph, captured on the second sighting of a
 # (device, x shape, alpha, callbacks) key; callbacks that are not the identity or graph_safe
 # (forward_tacotron.graph_safe) run eagerly between the replay and the launch that reads their
-# outputs (a split graph keyed without them).  FTMI_FP_GRAPH=0 keeps it eager.
+# outputs (a split graph keyed without them): phase_graph.  FTMI_FP_GRAPH=0 keeps it eager.
 FP_GRAPH = os.environ.get('FTMI_FP_GRAPH', '1') != '0'
-FP_GRAPH_CACHE = 8
-from .text.symbols import phonemes
 
 
 class PositionalEncoding(nn.Module):
@@ -112,16 +113,12 @@ class FFTBlock(Packed):
     def _panel_pack(self):
         """Fragment-major f16x3 planes of in_proj, out_proj and (kernel 1) conv2 — the
         operands of ops.panel_proj — cached like every pack (rebuilt with the params)."""
-        key = self._pack_key()
-        cache = self.__dict__.get('_ftmi_panel')
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                (wi, _, _), (wo, _, _), _, (w2, _, _) = self.packed_weights()
-                f16 = ops.split_weights_f16
-                cache = (key, (f16(wi, frag=True), f16(wo, frag=True),
-                               f16(w2, frag=True) if self.k2 == 1 else None))
-            self.__dict__['_ftmi_panel'] = cache
-        return cache[1]
+        def build():
+            (wi, _, _), (wo, _, _), _, (w2, _, _) = self.packed_weights()
+            f16 = ops.split_weights_f16
+            return (f16(wi, frag=True), f16(wo, frag=True),
+                    f16(w2, frag=True) if self.k2 == 1 else None)
+        return cached_pack(self, '_ftmi_panel', build)
 
     def forward_cl(self, x: torch.Tensor, kpm: Optional[torch.Tensor] = None) -> torch.Tensor:
         (wi, bi, si), (wo, bo, so), (w1, b1, s1), (w2, b2, s2) = self.packed_weights()
@@ -303,7 +300,6 @@ class FastPitch(nn.Module):
             cache[device] = [torch.cuda.Stream(device=device) for _ in range(3)]
         return cache[device]
 
-
     def __prepare_scriptable__(self):
         """`torch.jit.script(model)` (README.md:149-161 exports the reference this way) is not
         possible here: the compute runs in libftmi.so through ctypes, which TorchScript
@@ -312,6 +308,7 @@ class FastPitch(nn.Module):
         raise RuntimeError(f'{type(self).__name__} runs on libftmi.so (HIP kernels called through '
                            'ctypes) and cannot be compiled by torch.jit.script; call generate_jit / '
                            'generate eagerly')
+
     def generate(self,
                  x: torch.Tensor,
                  alpha=1.0,
@@ -371,76 +368,18 @@ class FastPitch(nn.Module):
                                 self.energy_strength)
         return dur_hat, pitch_hat, energy_hat, h, offsets, T_mel
 
-    def _weights_key(self):
-        """(data_ptr, _version) of every parameter and buffer (ForwardTacotron._weights_key)."""
-        return tuple((t.data_ptr(), t._version) for m in self.modules()
-                     for d in (m._parameters, m._buffers) for t in d.values() if t is not None)
-
     def _phase_graph(self, x, alpha, pitch_fn, energy_fn):
-        """The phoneme phase as a HIP graph (ForwardTacotron._phoneme_graph's protocol): a
-        key is captured the second time it is seen; x is copied into the static input; dur /
-        pitch / energy are cloned out; h and the offsets are consumed by this call's decoder
-        (the next replay waits for the decoder's completion event); a weights change drops
-        the captured phases.  Returns ((dur, pitch, energy, h, offsets, T_mel), entry) or
-        None (run the eager phase)."""
-        cache = self.__dict__.setdefault('_ftmi_graphs', {})
-        seen = self.__dict__.setdefault('_ftmi_graph_seen', {})
-        # callbacks not marked graph_safe run eagerly between the replay and the one launch
-        # that reads their outputs (ForwardTacotron._phoneme_graph's split graph)
-        split = not (_graphable(pitch_fn) and _graphable(energy_fn))
-        key = ((x.device, tuple(x.shape), float(alpha), 'split', ops.MMA) if split else
-               (x.device, tuple(x.shape), float(alpha), pitch_fn, energy_fn, ops.MMA))
-        cap_p, cap_e = (None, None) if split else (pitch_fn, energy_fn)
-        ent = cache.pop(key, None)
-        fresh = False
-        if ent is None:
-            n = seen.get(key, 0)
-            if n < 0:
-                return None
-            if len(seen) >= 64 * FP_GRAPH_CACHE:
-                seen.clear()
-            seen[key] = n + 1
-            if n == 0:
-                return None
-            wkey = self._weights_key()
-            sx = x.clone()
-            try:
-                self._phase(sx, alpha, cap_p, cap_e, capture=True)  # warm-up
-                torch.cuda.synchronize(x.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    outs = self._phase(sx, alpha, cap_p, cap_e, capture=True)
-            except Exception:  # pylint: disable=broad-except
-                torch.cuda.synchronize(x.device)
-                seen[key] = -1
-                return None
-            ent = {'g': g, 'sx': sx, 'outs': outs, 'wkey': wkey, 'done': torch.cuda.Event()}
-            ent['done'].record(torch.cuda.current_stream(x.device))
-            fresh = True
-            while len(cache) >= FP_GRAPH_CACHE:
-                cache.pop(next(iter(cache)))
-        cache[key] = ent
-        main = torch.cuda.current_stream(x.device)
-        main.wait_event(ent['done'])
-        ent['sx'].copy_(x)
-        ent['g'].replay()
-        if not fresh and self._weights_key() != ent['wkey']:
-            main.synchronize()
-            cache.clear()
-            return None
-        dur_hat, pitch_hat, energy_hat, h, offsets, tmax = ent['outs']
-        t_host = torch.empty((), dtype=tmax.dtype, pin_memory=True)
-        t_host.copy_(tmax, non_blocking=True)
-        t_ready = torch.cuda.Event()
-        t_ready.record(main)
-        dur_hat, pitch_hat, energy_hat = dur_hat.clone(), pitch_hat.clone(), energy_hat.clone()
-        if split:  # the callbacks on the predictors' outputs, then their projections
-            pitch_hat, energy_hat = pitch_fn(pitch_hat), energy_fn(energy_hat)
+        """The phoneme phase from its HIP graph (phase_graph.replay), keyed with the GEMM
+        matrix path.  The split graph leaves h without the pitch / energy projections: they
+        are added eagerly.  Returns ((dur, pitch, energy, h, offsets, T_mel), entry) or None
+        (run the eager phase)."""
+        def finish(phase):
             wp, bp, we, be = self._series_proj_weights()
-            ops.series_proj_add(h, pitch_hat, wp, bp, self.pitch_strength, energy_hat, we, be,
-                                self.energy_strength)
-        t_ready.synchronize()
-        return (dur_hat, pitch_hat, energy_hat, h, offsets, int(t_host)), ent
+            ops.series_proj_add(phase[3], phase[1], wp, bp, self.pitch_strength, phase[2], we,
+                                be, self.energy_strength)
+        return phase_graph.replay(
+            self, x, alpha, pitch_fn, energy_fn, (ops.MMA,),
+            lambda sx, p, e: self._phase(sx, alpha, p, e, capture=True), finish)
 
     def _generate(self, x, alpha, pitch_function, energy_function, batch):
         with torch.no_grad():

@@ -27,40 +27,20 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, chain, ops
+from . import _lib, chain, ops, phase_graph
 from .common_layers import (CBHG, BatchNormConv, BiRNN, Conv1dParams, LengthRegulator,
-                            LinearParams, Packed, pack_conv)
+                            LinearParams, Packed, cached_pack, pack_conv)
+from .phase_graph import _graphable, _identity, graph_safe  # noqa: F401  (public here)
 from .text.symbols import phonemes
 
 
-def _identity(t: torch.Tensor) -> torch.Tensor:
-    """The default pitch / energy callback (the reference's `lambda x: x`)."""
-    return t
-
-
-def graph_safe(fn: Callable[[torch.Tensor], torch.Tensor]) -> Callable[[torch.Tensor], torch.Tensor]:
-    """Mark a pitch / energy callback as safe to capture in the phoneme-phase HIP graph: a
-    pure function of its tensor argument made of device-side torch ops, whose behaviour
-    does not change between calls (no Python-side state it reads changes: closure
-    variables, attributes, scalars).  gen_forward.py's `lambda x: x * amp` is, for the run's
-    fixed `amp`.  An unmarked callback runs eagerly on every call, as the reference calls
-    it (`models/forward_tacotron.py:258-261`); returns fn."""
-    fn._ftmi_graph_safe = True
-    return fn
-
-
-def _graphable(fn) -> bool:
-    return fn is _identity or getattr(fn, '_ftmi_graph_safe', False) is True
-
-
 # generate() replays the phoneme phase as a HIP graph (captured per (device, x shape, alpha,
-# callbacks), see _phoneme_graph) when the phase is launch-bound: B*T <= GRAPH_MAX_TOKENS.
+# callbacks), see phase_graph) when the phase is launch-bound: B*T <= GRAPH_MAX_TOKENS.
 # Measured: c2 (B = 1, T = 120) 4.18 -> 3.57 ms/step; c3 (B = 64, T = 200) 9.20 -> 9.58, the
 # replay loses the prenet stream's priority and the kernels are long enough to hide the host
 # issue anyway.  FTMI_GRAPH=0, or GRAPH = False, keeps it eager.
 GRAPH = os.environ.get('FTMI_GRAPH', '1') != '0'
 GRAPH_MAX_TOKENS = int(os.environ.get('FTMI_GRAPH_MAX_TOKENS', 2048))
-GRAPH_CACHE = 8  # captured phases kept per model (least recently used dropped)
 
 
 class Embedding(nn.Module):
@@ -203,21 +183,18 @@ class ForwardTacotron(nn.Module):
         so the projection of enc can start as soon as the prenet ends and the predictors'
         outputs are added to its (B, T, 4H) rows afterwards (the same series_proj_add kernel
         with 4H-wide weights).  Made once per weights version, in float64."""
-        key = (self.lstm._pack_key(), self.pitch_proj.weight._version, self.pitch_proj.bias._version,
-               self.energy_proj.weight._version, self.energy_proj.bias._version,
-               self.pitch_proj.weight.data_ptr(), self.energy_proj.weight.data_ptr())
-        cache = self.__dict__.get('_ftmi_fold')
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                w_ih = self.lstm.packed_weights()[0].double()  # [2*4H][In], both directions
-                out = []
-                for w, b in (self.pitch_proj.weight, self.pitch_proj.bias), \
-                            (self.energy_proj.weight, self.energy_proj.bias):
-                    out.append((w_ih @ w.detach().double().reshape(-1, 3)).float().contiguous())
-                    out.append((w_ih @ b.detach().double()).float().contiguous())
-            cache = (key, tuple(out))
-            self.__dict__['_ftmi_fold'] = cache
-        return cache[1]
+        pp, ep = self.pitch_proj, self.energy_proj
+
+        def build():
+            w_ih = self.lstm.packed_weights()[0].double()  # [2*4H][In], both directions
+            out = []
+            for w, b in (pp.weight, pp.bias), (ep.weight, ep.bias):
+                out.append((w_ih @ w.detach().double().reshape(-1, 3)).float().contiguous())
+                out.append((w_ih @ b.detach().double()).float().contiguous())
+            return tuple(out)
+        return cached_pack(self.lstm, '_ftmi_fold', build, (
+            pp.weight._version, pp.bias._version, ep.weight._version, ep.bias._version,
+            pp.weight.data_ptr(), ep.weight.data_ptr()))
 
     def _encode(self, x: torch.Tensor, pitch: torch.Tensor, energy: torch.Tensor) -> torch.Tensor:
         """embedding -> prenet CBHG -> + pitch / energy projections: (B, T, 2*prenet_dims)."""
@@ -326,107 +303,18 @@ class ForwardTacotron(nn.Module):
             return [main, main, main]
         return cache[device]
 
-    def _weights_key(self):
-        """(data_ptr, _version) of every parameter and buffer: changes on load_state_dict,
-        .to(), in-place updates and replaced tensors (the list of tensors is cached and
-        rebuilt when an owner no longer holds the same object, like Packed._pack_key)."""
-        refs = self.__dict__.get('_ftmi_wrefs')
-        if refs is None or any(d.get(n) is not t for d, n, t in refs):
-            refs = [(d, n, t) for m in self.modules() for d in (m._parameters, m._buffers)
-                    for n, t in d.items() if t is not None]
-            self.__dict__['_ftmi_wrefs'] = refs
-        return tuple((t.data_ptr(), t._version) for _, _, t in refs)
-
     def _phoneme_graph(self, x, alpha, pitch_fn, energy_fn):
-        """The phoneme phase (unsharded) as a HIP graph: ~40 launches from Python over four
-        streams become one replay, which matters where the kernels are short (batch 1: the
-        host issue rate, not the device, set the phase's length).
-        Keyed on (device, x shape, alpha, the callbacks' identity, matrix paths); a key is
-        captured the SECOND time it is seen (a one-off shape — gen_forward.py's sentences
-        of different lengths — stays eager: capture costs ~3 eager phases).  The default
-        identity and callbacks marked `graph_safe` (pure device-side torch ops whose effect
-        does not change between calls) are captured with the phase.  Any other callback —
-        gen_forward.py's plain `lambda x: x * amp` — splits it: the graph holds everything
-        but the callbacks and the one launch that reads their outputs (the pitch / energy
-        projections added to the LSTM input projection, series_proj_add); after each replay
-        the callbacks run eagerly on the predictors' outputs (fresh tensors, on the caller's
-        stream), as the reference calls them, and that launch follows.  The split graph is
-        keyed without the callbacks' identity (they are not in it).  FTMI_GRAPH=0 (or
-        forward_tacotron.GRAPH = False) turns capture
-        off.  A capture that fails (a callback that syncs or leaves the device) marks the
-        key eager for good.
-        Static buffers: x is copied in, dur / pitch / energy are cloned out (they go back to
-        the caller); enc, the offsets and the LSTM input projection are consumed by this
-        call's decoder — the next replay waits for the decoder's completion event
-        (generate() records it), so calls on different streams never overwrite buffers a
-        decoder still reads.  The entry keeps every module's weight packs (the fused-stack blocks and the
-        table-gather bank's table too) alive and the
-        model-wide weights key of its capture: after each replay (while it runs) the key is
-        compared with the model's, and on a change (load_state_dict, .to(), in-place
-        updates) every captured phase is dropped and the call falls back to the eager phase
-        (the stale replay read the old, still-allocated packs; its outputs are discarded).
-        Returns (phase outputs, entry) or None (run the eager phase)."""
-        cache = self.__dict__.setdefault('_ftmi_graphs', {})
-        seen = self.__dict__.setdefault('_ftmi_graph_seen', {})
-        # split: a callback that is not graph_safe runs eagerly between the captured
-        # predictors and the one launch that consumes its output (series_proj_add)
-        split = not (_graphable(pitch_fn) and _graphable(energy_fn))
-        key = ((x.device, tuple(x.shape), float(alpha), 'split', ops.MMA, ops.RNN_MMA) if split else
-               (x.device, tuple(x.shape), float(alpha), pitch_fn, energy_fn, ops.MMA, ops.RNN_MMA))
-        cap_p, cap_e = (None, None) if split else (pitch_fn, energy_fn)
-        ent = cache.pop(key, None)
-        fresh = False
-        if ent is None:
-            n = seen.get(key, 0)
-            if n < 0:
-                return None  # capture failed before: eager for good
-            if len(seen) >= 64 * GRAPH_CACHE:  # e.g. a new lambda per call: forget sightings
-                seen.clear()
-            seen[key] = n + 1
-            if n == 0:
-                return None  # first sighting: eager
-            wkey = self._weights_key()
-            sx = x.clone()
-            try:
-                self._phoneme_phase(sx, alpha, cap_p, cap_e, capture=True)  # warm-up
-                torch.cuda.synchronize(x.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    outs = self._phoneme_phase(sx, alpha, cap_p, cap_e, capture=True)
-            except Exception:  # pylint: disable=broad-except
-                torch.cuda.synchronize(x.device)
-                seen[key] = -1
-                return None
-            packs = [m.__dict__.get(k) for m in self.modules()
-                     for k in ('_ftmi_pack', '_ftmi_stack', '_ftmi_embed_table')]
-            ent = {'g': g, 'sx': sx, 'outs': outs, 'wkey': wkey, 'packs': packs,
-                   'done': torch.cuda.Event()}
-            ent['done'].record(torch.cuda.current_stream(x.device))
-            fresh = True
-            while len(cache) >= GRAPH_CACHE:
-                cache.pop(next(iter(cache)))
-        cache[key] = ent  # most recently used last
-        main = torch.cuda.current_stream(x.device)
-        main.wait_event(ent['done'])  # the previous decoder is done with the static buffers
-        ent['sx'].copy_(x)
-        ent['g'].replay()
-        if not fresh and self._weights_key() != ent['wkey']:
-            main.synchronize()  # the stale replay must finish before its graph is freed
-            cache.clear()
-            return None
-        dur_hat, pitch_hat, energy_hat, enc, offsets, tmax, xp = ent['outs']
-        t_host = torch.empty((), dtype=tmax.dtype, pin_memory=True)
-        t_host.copy_(tmax, non_blocking=True)
-        t_ready = torch.cuda.Event()
-        t_ready.record(main)
-        dur_hat, pitch_hat, energy_hat = dur_hat.clone(), pitch_hat.clone(), energy_hat.clone()
-        if split:  # the callbacks on the predictors' outputs, then their projections
-            pitch_hat, energy_hat = pitch_fn(pitch_hat), energy_fn(energy_hat)
+        """The phoneme phase (unsharded) from its HIP graph (phase_graph.replay: ~40 launches
+        from Python become one replay), keyed with both matrix paths.  The split graph
+        leaves xp without the pitch / energy terms: they are added eagerly, folded through
+        W_ih.  Returns (phase outputs, entry) or None (run the eager phase)."""
+        def finish(phase):
             wp, bp, we, be = self._folded_series_weights()
-            ops.series_proj_add(xp, pitch_hat, wp, bp, self.pitch_strength, energy_hat, we,
+            ops.series_proj_add(phase[6], phase[1], wp, bp, self.pitch_strength, phase[2], we,
                                 be, self.energy_strength)
-        t_ready.synchronize()
-        return (dur_hat, pitch_hat, energy_hat, enc, offsets, int(t_host), xp), ent
+        return phase_graph.replay(
+            self, x, alpha, pitch_fn, energy_fn, (ops.MMA, ops.RNN_MMA),
+            lambda sx, p, e: self._phoneme_phase(sx, alpha, p, e, capture=True), finish)
 
     def _phoneme_phase(self, x, alpha, pitch_fn, energy_fn, batch=None, capture=False):
         """Duration / pitch / energy predictors and the prenet CBHG are independent: pitch,
@@ -442,10 +330,10 @@ class ForwardTacotron(nn.Module):
         with every tensor ready on the caller's stream (xp: the LSTM input projection of enc
         plus the pitch / energy projections, folded through W_ih; enc itself does not carry
         them; index: the LR index map, queued on the caller's stream before it joins the side
-        streams).  capture=True (graph capture, see _phoneme_graph): no host sync, the T_mel
+        streams).  capture=True (graph capture, see phase_graph): no host sync, the T_mel
         slot holds max(totals) on the device and the offsets slot plain offsets.
         pitch_fn = energy_fn = None (capture only): the predictors' raw outputs are returned
-        and xp does not carry their projections yet (the split graph of _phoneme_graph)."""
+        and xp does not carry their projections yet (the split graph of phase_graph)."""
         main = torch.cuda.current_stream(x.device)
         s_pitch, s_energy, s_prenet = self._side_streams(x.device, x.size(0), x.size(1))
         for s in (s_pitch, s_energy, s_prenet):

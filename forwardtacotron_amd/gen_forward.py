@@ -238,7 +238,7 @@ def main(argv: Optional[Sequence[str]] = None) -> List[Path]:
     tts_k = tts_model.get_step() // 1000
     texts = read_inputs(args)
     # gen_forward.py:103-104, the same plain lambdas: generate() replays the phoneme phase
-    # from its split graph and runs them eagerly in between (forward_tacotron._phoneme_graph)
+    # from its split graph and runs them eagerly in between (phase_graph)
     pitch_function = lambda x: x * args.amp  # noqa: E731
     energy_function = lambda x: x  # noqa: E731
     from .host_io import PinnedD2H

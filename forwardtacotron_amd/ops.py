@@ -433,7 +433,7 @@ def conv_bank(x: torch.Tensor, w: torch.Tensor, K: int, Cout: int, scale: torch.
     sk, part = r.split_k, None
     if r.kernel == _lib.ROUTE_BANK_HALVES:
         # the few-row bank in one launch (gemm.hip conv_bank_halves_kernel)
-        part, flags = _bank_workspace(r.ws_floats - BANK_COUNTERS, x.device), BANK_HALVES
+        part, flags = _stream_workspace('bank', r.ws_floats, x.device, _f32), BANK_HALVES
         if w_image is not None:
             _dev(w_image)
             wsp, flags = w_image.data_ptr(), BANK_HALVES | BANK_IMAGE
@@ -469,25 +469,30 @@ def _bank_halves(mma: int, B: int, T: int, Cin: int, K: int, Cout: int) -> bool:
     return _bank_route(mma, B, T, Cin, K, Cout).kernel == _lib.ROUTE_BANK_HALVES
 
 
-_BANK_WS = {}
+_STREAM_WS = {}      # (kind, device, stream handle) -> that stream's workspace of the kind
+_STREAM_WS_OLD = []  # superseded ones: queued work or a captured graph may still use them
 
 
-def _bank_workspace(n_part: int, device) -> torch.Tensor:
-    """The FTMI_BANK_HALVES workspace of the current stream: BANK_COUNTERS counters (zero
-    once; every launch leaves them zero) followed by n_part floats of partial sums.  One per
-    (device, stream) — launches on one stream are ordered, so they may share it — kept alive
-    for graph replays that captured its address; grown (a new zeroed buffer) when too small."""
-    stream = torch.cuda.current_stream(device)
-    key = (torch.device(device), stream.cuda_stream)
-    t = _BANK_WS.get(key)
-    if t is None or t.numel() < BANK_COUNTERS + n_part:
-        if t is not None:  # the old buffer may still be in use by queued work
-            _BANK_OLD.append(t)
-        t = _BANK_WS[key] = torch.zeros(BANK_COUNTERS + n_part, device=device, dtype=_f32)
+def _stream_workspace(kind: str, n: int, device, dtype=torch.uint8) -> torch.Tensor:
+    """The current stream's zeroed workspace of a kind, at least n elements of dtype.  One per
+    (kind, device, stream) — launches on one stream are ordered, so they may share it — kept
+    alive for graph replays that captured its address; grown (a new zeroed buffer, the old
+    one retired to _STREAM_WS_OLD) when too small.  The kinds:
+    'bank'    FTMI_BANK_HALVES: BANK_COUNTERS fp32 counters (zero once; every launch leaves
+              them zero) followed by the partial sums;
+    'spread'  the spread CBHG tail's exchange bytes;
+    'kv'      the attention K / V planes (ftmi_panel_proj_qkv / ftmi_attention_kv), shared by
+              the layers on a stream.  The planes' pad keys T..Tp-1 are never written; the
+              attention kernels zero them while staging (a stale value there, even an inf
+              left by an overflowing call that reran on the exact path, never reaches the
+              output)."""
+    key = (kind, torch.device(device), torch.cuda.current_stream(device).cuda_stream)
+    t = _STREAM_WS.get(key)
+    if t is None or t.numel() < n:
+        if t is not None:
+            _STREAM_WS_OLD.append(t)
+        t = _STREAM_WS[key] = torch.zeros(n, device=device, dtype=dtype)
     return t
-
-
-_BANK_OLD = []  # superseded workspaces (kept: a captured graph may still replay them)
 
 
 def split_rows(x: torch.Tensor) -> torch.Tensor:
@@ -632,7 +637,8 @@ def highway_stack(x: torch.Tensor, pre_split: torch.Tensor, C: int, hw_splits, b
             n_out if out_split is not None else 0, _ptr(y), y.stride(1) if y is not None else 0,
             _ptr(h), h.stride(1) if h is not None else 0, status_word(x.device).data_ptr())
     if spread and hs_spread_blocks(M, n_out if out_split is not None else 0) > 0:
-        ws = _spread_workspace(int(_lib.load().ftmi_highway_stack_spread_ws_bytes(M)), x.device)
+        nws = int(_lib.load().ftmi_highway_stack_spread_ws_bytes(M))
+        ws = _stream_workspace('spread', max(nws, 16), x.device)
         launch('ftmi_highway_stack_spread', f'highway_stack_spread[M={M},Cp={Cp},L={L},N={n_out}]',
                flops, nbytes, *args, ws.data_ptr(), _stream())
     else:
@@ -649,23 +655,6 @@ def hs_spread_blocks(M: int, n_out: int = 0) -> int:
         return 0
     n = int(_lib.load().ftmi_highway_stack_spread_blocks(M))
     return n if 0 < n <= _num_cus() else 0
-
-
-_SPREAD_WS = {}
-
-
-def _spread_workspace(nbytes: int, device) -> torch.Tensor:
-    """The spread tail's exchange workspace of the current stream (one per (device, stream):
-    launches on one stream are ordered), kept alive for graph replays that captured its
-    address; grown when too small."""
-    stream = torch.cuda.current_stream(device)
-    key = (torch.device(device), stream.cuda_stream)
-    t = _SPREAD_WS.get(key)
-    if t is None or t.numel() < nbytes:
-        if t is not None:
-            _BANK_OLD.append(t)  # a captured graph may still replay the old buffer
-        t = _SPREAD_WS[key] = torch.zeros(max(nbytes, 16), device=device, dtype=torch.uint8)
-    return t
 
 
 PANEL_N = 256  # gemm.hip panel_proj_kernel: output columns per panel (LayerNorm width)
@@ -711,28 +700,6 @@ def panel_proj(x: torch.Tensor, w_frag: torch.Tensor, N: int, bias: Optional[tor
     return y
 
 
-_KV_WS = {}
-
-
-def _kv_workspace(nbytes: int, device) -> torch.Tensor:
-    """The attention K / V plane workspace of the current stream (ftmi_panel_proj_qkv /
-    ftmi_attention_kv), reused by every call on the stream (stream order separates the
-    layers' uses); grown when too small.  The planes' pad keys T..Tp-1 are never written;
-    the attention kernels zero them while staging (a stale value there, even an inf left by
-    an overflowing call that reran on the exact path, never reaches the output)."""
-    stream = torch.cuda.current_stream(device)
-    key = (torch.device(device), stream.cuda_stream)
-    t = _KV_WS.get(key)
-    if t is None or t.numel() < nbytes:
-        if t is not None:
-            _KV_OLD.append(t)  # may still be read by queued work
-        t = _KV_WS[key] = torch.zeros(nbytes, device=device, dtype=torch.uint8)
-    return t
-
-
-_KV_OLD = []
-
-
 def kv_fused_ok(T: int, d: int, heads: int, w_frag) -> bool:
     """Whether FastPitch's in_proj + attention take ftmi_panel_proj_qkv + ftmi_attention_kv
     (the split pass folded into the projection): f16x3 in force, the attention would
@@ -750,7 +717,7 @@ def panel_proj_qkv(x: torch.Tensor, w_frag: torch.Tensor, d: int, heads: int,
     B, T, K, xs = _rows(x)
     q = torch.empty(B, T, d, device=x.device, dtype=_f32)
     nws = int(_lib.load().ftmi_attention_workspace_bytes(B, T, heads, d // heads))
-    ws = _kv_workspace(nws, x.device)
+    ws = _stream_workspace('kv', nws, x.device)
     launch('ftmi_panel_proj_qkv', f'panel_proj[M={B * T},K={K},N={3 * d},qkv]',
            2.0 * B * T * 3 * d * K, 4.0 * B * T * (K + d) + 2.0 * nws / 4 * 2,
            x.data_ptr(), xs, B, T, K, w_frag.data_ptr(), d, _ptr(bias), heads, q.data_ptr(),

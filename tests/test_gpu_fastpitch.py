@@ -217,6 +217,71 @@ def test_graph_phase_matches_eager(fp_model, monkeypatch):
             assert torch.equal(o[k], ref[k]), (a, k)
 
 
+def _fresh_graphs(m):
+    for k in ('_ftmi_graphs', '_ftmi_graph_seen'):
+        m.__dict__.pop(k, None)
+
+
+def test_graph_sees_new_weights(fp_model, monkeypatch):
+    """test_gpu_model.py::test_graph_sees_new_weights for FastPitch: a captured phase must not
+    replay stale weights.  Capture, load a different state_dict, generate again: the result
+    equals the eager path with the new weights and differs from the old; an in-place update
+    of one predictor weight is seen too; restoring the weights gives the first result bit
+    for bit."""
+    from forwardtacotron_amd import fast_pitch as FPM
+    from forwardtacotron_amd.synthetic import synthetic_state_dict
+    m, sd = fp_model
+    x = dev(load_golden('fp_gen_b3')['x'])
+    monkeypatch.setattr(FPM, 'FP_GRAPH', True)
+    _fresh_graphs(m)
+    a = [m.generate(x) for _ in range(3)]  # eager, capture, replay
+    assert len(m.__dict__['_ftmi_graphs']) == 1
+    other = {k: torch.from_numpy(v) for k, v in synthetic_state_dict(m, 1, 'fast_pitch').items()}
+    try:
+        m.load_state_dict(other)
+        b = m.generate(x)
+        monkeypatch.setattr(FPM, 'FP_GRAPH', False)
+        b_eager = m.generate(x)
+        monkeypatch.setattr(FPM, 'FP_GRAPH', True)
+        for k in ('mel', 'dur', 'pitch', 'energy'):
+            assert torch.equal(b[k], b_eager[k]), k
+        assert not torch.equal(b['dur'], a[0]['dur'])
+        # in-place update of one predictor weight (no load_state_dict): also seen
+        c0 = m.generate(x)
+        with torch.no_grad():
+            m.pitch_pred.lin.weight.mul_(0.5)
+        c1 = m.generate(x)
+        assert not torch.equal(c0['pitch'], c1['pitch'])
+    finally:
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    d = m.generate(x)
+    for k in ('mel', 'dur', 'pitch', 'energy'):
+        assert torch.equal(d[k], a[0][k]), k
+
+
+def test_graph_entry_holds_packs(fp_model, monkeypatch):
+    """A captured phase keeps the weight packs its kernels point into alive (the entry's
+    'packs', common_layers.held_packs): a teacher-forced forward() after load_state_dict
+    rebuilds the packs, and the stale replay that follows must not read freed memory.  The
+    entry holds every module's packed_weights() tensors and the FFT blocks' panel planes."""
+    from forwardtacotron_amd import fast_pitch as FPM
+    from forwardtacotron_amd.chain import _flatten
+    m, _ = fp_model
+    x = dev(load_golden('fp_gen_b3')['x'])
+    monkeypatch.setattr(FPM, 'FP_GRAPH', True)
+    _fresh_graphs(m)
+    for _ in range(2):  # eager, capture
+        m.generate(x)
+    (ent,) = m.__dict__['_ftmi_graphs'].values()
+    held = {t.data_ptr() for t in _flatten(ent['packs'])}
+    block = m.prenet.layers[0]
+    for t in _flatten([block.packed_weights(), m.lin.packed_weights(),
+                       m.pitch_pred.transformer.layers[-1].packed_weights()]):
+        assert t.data_ptr() in held
+    planes = _flatten(block._panel_pack())
+    assert planes and all(t.data_ptr() in held for t in planes)
+
+
 def test_panel_path_matches_unfused(fp_model, monkeypatch):
     """The FFT blocks' row-panel launches (ops.panel_proj: in_proj, out_proj + norm1, conv2
     + norm2) against the slab GEMM + layernorm launches (FTMI_PANEL=0).  The projections agree

@@ -298,11 +298,36 @@ def test_conv_bank_halves(K, Cin, B, T, rng, monkeypatch):
         yi = ops.conv_bank(x, wp, K, C, sc, sh, mma=2, w_split=w3, w_image=img)
         np.testing.assert_array_equal(host(yi), a0)
     assert int(st.item()) == 0
-    key = (torch.device('cuda', torch.cuda.current_device()), torch.cuda.current_stream().cuda_stream)
-    assert not ops._BANK_WS[key][:ops.BANK_COUNTERS].any()  # counters back to zero
+    key = ('bank', torch.device('cuda', torch.cuda.current_device()),
+           torch.cuda.current_stream().cuda_stream)
+    assert not ops._STREAM_WS[key][:ops.BANK_COUNTERS].any()  # counters back to zero
     monkeypatch.setenv('FTMI_BANK_HALVES', '0')
     b0 = host(ops.conv_bank(x, wp, K, C, sc, sh, mma=2, w_split=w3))
     close(a0, b0, rtol=1e-5, atol=1e-5)
+
+
+def test_stream_workspace():
+    """ops._stream_workspace (the halves bank's, the spread tail's and the K / V planes'
+    buffer): one zeroed buffer per (kind, device, stream), reused while it is large enough;
+    a larger request gets a new zeroed buffer and the old one stays referenced (a captured
+    graph may replay its address); another stream or kind gets its own."""
+    from forwardtacotron_amd import ops
+    kind, dev0 = 'test_stream_workspace', torch.device('cuda', torch.cuda.current_device())
+    a = ops._stream_workspace(kind, 1000, dev0)
+    assert a.dtype == torch.uint8 and a.numel() >= 1000 and not a.any()
+    assert ops._stream_workspace(kind, 10, dev0) is a
+    a.fill_(7)
+    b = ops._stream_workspace(kind, 1001, dev0)
+    assert b is not a and b.data_ptr() != a.data_ptr() and b.numel() >= 1001 and not b.any()
+    assert any(t is a for t in ops._STREAM_WS_OLD)
+    assert ops._stream_workspace(kind, 1000, dev0) is b
+    with torch.cuda.stream(torch.cuda.Stream()):
+        c = ops._stream_workspace(kind, 10, dev0)
+        assert ops._stream_workspace(kind, 10, dev0) is c
+    assert c is not b and c.data_ptr() != b.data_ptr() and not c.any()
+    f = ops._stream_workspace(kind + '_f32', 12, dev0, torch.float32)
+    assert f.dtype == torch.float32 and f.numel() >= 12 and not f.any()
+    assert ops._stream_workspace(kind, 10, dev0) is b
 
 
 def test_conv_bank_halves_range_guard(rng):

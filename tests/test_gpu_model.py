@@ -481,6 +481,27 @@ def test_graph_sees_new_weights(gpu_model, synth_sd, monkeypatch):
     assert torch.equal(d['mel_post'], a[0]['mel_post'])
 
 
+def test_graph_entry_holds_packs(gpu_model, monkeypatch):
+    """A captured phase keeps the weight packs its kernels point into alive (the entry's
+    'packs', common_layers.held_packs): every module's packed_weights() tensors and the
+    prenet's fused-stack planes, found through the pack cache, not a list of slot names."""
+    from forwardtacotron_amd import forward_tacotron as FT
+    from forwardtacotron_amd.chain import _flatten
+    x = torch.from_numpy(load_golden('gen_b3')['x']).cuda()
+    monkeypatch.setattr(FT, 'GRAPH', True)
+    _fresh_graphs(gpu_model)
+    for _ in range(2):  # eager, capture
+        gpu_model.generate(x)
+    (ent,) = gpu_model.__dict__['_ftmi_graphs'].values()
+    held = {t.data_ptr() for t in _flatten(ent['packs'])}
+    for t in _flatten([gpu_model.prenet.packed_weights(), gpu_model.lstm.packed_weights(),
+                       gpu_model.dur_pred.convs[0].packed_weights(),
+                       gpu_model.lin.packed_weights()]):
+        assert t.data_ptr() in held
+    planes = _flatten(gpu_model.prenet._stack_pack())
+    assert planes and all(t.data_ptr() in held for t in planes)
+
+
 def test_recurrence_timeout_raises(gpu_model, monkeypatch):
     """a recurrence workgroup that gives up waiting must fail the call
     (ops.RnnTimeout), not return garbage with status 0.  A spin bound of 1 poll forces
