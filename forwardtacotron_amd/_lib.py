@@ -222,6 +222,11 @@ SIGNATURES = {
     'ftmi_nnls_lbfgsb_start': (c_int, [ctypes.POINTER(NnlsArgs), P]),
     'ftmi_nnls_lbfgsb_cycles': (c_int, [ctypes.POINTER(NnlsArgs), c_int, P]),
     'ftmi_nnls_lbfgsb_finish': (c_int, [ctypes.POINTER(NnlsArgs), P, P, P, P]),
+    'ftmi_frame_power': (c_int, [P, c_int64, c_int, c_int64, P, c_int, c_int, c_int, P, P]),
+    'ftmi_trim_bounds': (c_int, [P, c_int, c_int, c_int64, P, c_int, ctypes.c_double, P, P]),
+    'ftmi_peak_abs': (c_int, [P, c_int64, c_int, c_int64, P, P, P]),
+    'ftmi_prepare_audio': (c_int, [P, c_int64, c_int, c_int64, P, P, c_int, c_int, c_int, P,
+                                   c_int64, P, c_int64, P, P]),
 }
 
 

@@ -72,3 +72,13 @@ static inline S ftmi_read_switches(const ftmi_switch<S> (&table)[N]) {
 }
 
 __device__ __forceinline__ float ftmi_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// numpy.pad(mode='reflect') index for any pad width (periodic reflection, period 2(L-1));
+// shared by the STFT framing (dsp.hip) and the silence trim's frame power (prep.hip)
+__device__ __forceinline__ int64_t reflect_index(int64_t j, int64_t L) {
+  if (L <= 1) return 0;
+  const int64_t per = 2 * (L - 1);
+  j %= per;
+  if (j < 0) j += per;
+  return j >= L ? per - j : j;
+}

@@ -57,15 +57,6 @@ __device__ double2 *fft_lds(double2 *a, double2 *y, const FftPlan &P) {
   return a;
 }
 
-// numpy.pad(mode='reflect') index for any pad width (periodic reflection, period 2(L-1))
-__device__ __forceinline__ int64_t reflect_index(int64_t j, int64_t L) {
-  if (L <= 1) return 0;
-  const int64_t per = 2 * (L - 1);
-  j %= per;
-  if (j < 0) j += per;
-  return j >= L ? per - j : j;
-}
-
 // correctly rounded |re + i im| of a complex64 value
 __device__ __forceinline__ float cabs_rn(float re, float im) {
   return (float)sqrt((double)re * (double)re + (double)im * (double)im);

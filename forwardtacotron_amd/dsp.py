@@ -11,11 +11,19 @@ and pseudo-inverse) and moves arrays between numpy and the device, so
 keep the reference's signatures.  The batched device entry points
 (``mel_spectrogram`` / ``griffinlim_batch``) take and return HIP tensors.
 
-Not carried over (outside the hot path, need absent libraries): ``load_wav`` resampling
-(librosa), ``trim_silence`` (librosa.effects), ``trim_long_silences`` (webrtcvad).
+The preparation stage of the reference's ``preprocess.py`` runs here too (``csrc/prep.hip``):
+``trim_silence`` is librosa 0.7.2 ``effects.trim`` restated (``frame_power`` /
+``trim_bounds``), and ``prepare_batch`` / ``prepare_wav`` are ``Preprocessor._convert_file``
+without the pitch track: trim, peak rule, log-mel and the vocoder's label sequence, for a
+batch of rows with no host synchronisation.  ``python -m forwardtacotron_amd.preprocess``
+is the command-line form.
+
+Not carried over (need absent libraries): ``load_wav`` resampling (librosa),
+``trim_long_silences`` (webrtcvad), the ``dio`` pitch track (pyworld).
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import wave
@@ -152,18 +160,21 @@ def stft(plan: DspPlan, y: torch.Tensor, lengths: Optional[torch.Tensor] = None)
 
 
 def mel_spectrogram(plan: DspPlan, y: torch.Tensor, lengths: Optional[torch.Tensor] = None,
-                    log_norm: bool = True) -> torch.Tensor:
-    """Batched DSP.wav_to_mel: audio rows (B, L) float32 -> (B, n_mels, 1 + L // hop)."""
-    _need_cuda(y, lengths)
+                    log_norm: bool = True, frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Batched DSP.wav_to_mel: audio rows (B, L) float32 -> (B, n_mels, 1 + L // hop).
+    frames (int32 [B], optional): item b gets its first frames[b] frames and zeros after them.
+    The kernel transforms frames in pairs, so an item's last frame is bit-equal to the one
+    wav_to_mel makes of that item alone only when its own frame count is given."""
+    _need_cuda(y, lengths, frames)
     if y.dtype != torch.float32 or y.dim() != 2 or y.stride(1) != 1:
         raise ValueError('audio rows (B, L) float32 with unit stride expected')
     B, L = y.shape
     F = plan.frames(L)
-    mel = torch.empty(B, plan.n_mels, F, device=y.device)
+    mel = (torch.empty if frames is None else torch.zeros)(B, plan.n_mels, F, device=y.device)
     launch('ftmi_mel_spectrogram', f'mel_spectrogram[B={B},F={F},n={plan.n_fft}]', 0,
            4.0 * B * L + 4.0 * B * F * plan.n_mels,
            y.data_ptr(), y.stride(0), B, L, _p(lengths), plan.n_fft, plan.hop,
-           plan.window.data_ptr(), plan.twiddle.data_ptr(), F, None, plan.basis.data_ptr(),
+           plan.window.data_ptr(), plan.twiddle.data_ptr(), F, _p(frames), plan.basis.data_ptr(),
            plan.mel_lo.data_ptr(), plan.mel_hi.data_ptr(), plan.n_mels, int(log_norm),
            mel.data_ptr(), _stream())
     return mel
@@ -352,6 +363,67 @@ def _gl_loop(plan: DspPlan, S: torch.Tensor, angles: torch.Tensor, n_iter: int,
     return istft(plan, X, frames, L, work)
 
 
+# --- audio preparation (csrc/prep.hip) --------------------------------------------------------
+
+def _rows(y: torch.Tensor, lengths: Optional[torch.Tensor]):
+    _need_cuda(y, lengths)
+    if y.dtype != torch.float32 or y.dim() != 2 or y.stride(1) != 1:
+        raise ValueError('audio rows (B, L) float32 with unit stride expected')
+    if lengths is not None:
+        if lengths.shape != (y.shape[0],):
+            raise ValueError('lengths: one entry per row expected')
+        lengths = lengths.to(device=y.device, dtype=torch.int32).contiguous()
+    return y.shape[0], y.shape[1], lengths
+
+
+def frame_power(y: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                frame_length: int = 2048, hop_length: int = 512) -> torch.Tensor:
+    """Mean square of every centred, reflect-padded frame of audio rows (B, L): (B, 1 + L // hop)
+    float32, fp64 sums in a fixed order rounded once; zero past an item's own 1 + L_b // hop
+    frames.  (librosa feature.rms squared, without its float32 mean and sqrt-then-square.)"""
+    B, L, lengths = _rows(y, lengths)
+    F = 1 + L // max(hop_length, 1)
+    power = torch.empty(B, F, device=y.device)
+    launch('ftmi_frame_power', f'frame_power[B={B},F={F},n={frame_length},hop={hop_length}]', 0,
+           4.0 * B * L + 4.0 * B * F,
+           y.data_ptr(), y.stride(0), B, L, _p(lengths), frame_length, hop_length, F,
+           power.data_ptr(), _stream())
+    return power
+
+
+def _bounds_of_power(power: torch.Tensor, L: int, lengths: Optional[torch.Tensor], hop: int,
+                     top_db: float) -> torch.Tensor:
+    B, F = power.shape
+    bounds = torch.empty(B, 2, dtype=torch.int32, device=power.device)
+    launch('ftmi_trim_bounds', f'trim_bounds[B={B},F={F}]', 0, 8.0 * B * F + 8.0 * B,
+           power.data_ptr(), B, F, L, _p(lengths), hop, ctypes.c_double(top_db),
+           bounds.data_ptr(), _stream())
+    return bounds
+
+
+def trim_bounds(y: torch.Tensor, lengths: Optional[torch.Tensor] = None, top_db: float = 60,
+                frame_length: int = 2048, hop_length: int = 512) -> torch.Tensor:
+    """librosa 0.7.2 effects.trim's interval of every row of (B, L): (B, 2) int32 [start, end),
+    each item against its own loudest frame.  (0, 0) when no frame is over the threshold; an
+    all-zero item ties its reference at the floor and keeps (0, L_b)."""
+    B, L, lengths = _rows(y, lengths)
+    power = frame_power(y, lengths, frame_length, hop_length)
+    return _bounds_of_power(power, L, lengths, hop_length, float(top_db))
+
+
+def peak_abs(y: torch.Tensor, bounds: torch.Tensor) -> torch.Tensor:
+    """max |y| over each row's [start, end): (B,) float32."""
+    B, L, _ = _rows(y, None)
+    peak = torch.empty(B, device=y.device)
+    launch('ftmi_peak_abs', f'peak_abs[B={B},L={L}]', 0, 4.0 * B * L + 4.0 * B,
+           y.data_ptr(), y.stride(0), B, L, bounds.data_ptr(), peak.data_ptr(), _stream())
+    return peak
+
+
+PreparedBatch = collections.namedtuple(
+    'PreparedBatch', ['wav', 'lengths', 'mel', 'frames', 'quant', 'bounds', 'peak'])
+
+
 # --- the reference class ---------------------------------------------------------------------
 
 class DSP:
@@ -526,13 +598,95 @@ class DSP:
     def denormalize(self, mel):
         return torch.exp(mel) if isinstance(mel, torch.Tensor) else np.exp(mel)
 
-    def trim_silence(self, wav: np.ndarray) -> np.ndarray:
-        raise NotImplementedError('trim_silence needs librosa.effects (absent); preprocessing '
-                                  'is outside the inference path')
+    # -- utils/dsp.py:112-113 --
+    TRIM_FRAME_LENGTH, TRIM_HOP_LENGTH = 2048, 512  # librosa effects.trim's defaults
+
+    def trim_silence(self, wav):
+        """librosa.effects.trim(wav, top_db=trim_silence_top_db, frame_length=2048,
+        hop_length=512)[0]: numpy (L,) -> the numpy slice; a HIP tensor (L,) -> the tensor
+        slice (one read of the two bounds)."""
+        is_t = isinstance(wav, torch.Tensor)
+        if is_t:
+            _need_cuda(wav)
+            if wav.dim() != 1:
+                raise ValueError('mono audio (L,) expected')
+            t = wav.float().contiguous()[None]
+        else:
+            wav = np.asarray(wav)
+            if not np.issubdtype(wav.dtype, np.floating) or wav.ndim != 1:
+                raise ValueError('mono floating-point audio expected')
+            t = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)).cuda()[None]
+        s, e = trim_bounds(t, None, self.trim_silence_top_db, self.TRIM_FRAME_LENGTH,
+                           self.TRIM_HOP_LENGTH)[0].tolist()
+        return wav[s:e]
 
     def trim_long_silences(self, wav: np.ndarray) -> np.ndarray:
-        raise NotImplementedError('trim_long_silences needs webrtcvad (absent); preprocessing '
-                                  'is outside the inference path')
+        raise NotImplementedError('trim_long_silences needs webrtcvad (absent)')
+
+    # -- preprocess.py:51-91 (Preprocessor._convert_file without the pitch track) --
+    def label_mode(self) -> Tuple[bool, int]:
+        """(mu_law, bits) of the vocoder's label sequence (preprocess.py:83-89)."""
+        if self.voc_mode == 'RAW':
+            return bool(self.mu_law), int(self.bits)
+        if self.voc_mode == 'MOL':
+            return False, 16
+        raise ValueError(f'Unexpected voc mode {self.voc_mode}, should be either RAW or MOL.')
+
+    def prepare_batch(self, wavs: torch.Tensor,
+                      lengths: Optional[torch.Tensor] = None) -> PreparedBatch:
+        """Preprocessor._convert_file of every row of wavs (B, L) float32 (item b: its first
+        lengths[b] samples), queued on the current stream without a host synchronisation:
+
+          wav     (B, L) float32  the trimmed samples left-aligned, divided by the item's peak
+                                  when peak_norm is set or the peak is above 1, zeros after
+          lengths (B,) int32      samples per prepared item
+          mel     (B, n_mels, 1 + L // hop)  wav_to_mel of each prepared item, zeros past its frames
+          frames  (B,) int32      1 + lengths // hop
+          quant   (B, L) int64    the vocoder labels (mu-law / RAW bits / MOL 16 bits), zeros after
+          bounds  (B, 2) int32    [start, end) kept of each input row
+          peak    (B,) float32    max |y[start:end]|
+
+        The trim runs when trim_start_end_silence is set.  trim_long_silences=True raises: the
+        reference tests the bound method there (always true); the config flag is followed
+        here.  An all-zero item is left unscaled (the reference divides it by zero)."""
+        if self.should_trim_long_silences:
+            raise NotImplementedError('trim_long_silences needs webrtcvad (absent)')
+        mu_law, bits = self.label_mode()
+        B, L, lengths = _rows(wavs, lengths)
+        dev = wavs.device
+        if self.should_trim_start_end_silence:
+            bounds = trim_bounds(wavs, lengths, self.trim_silence_top_db, self.TRIM_FRAME_LENGTH,
+                                 self.TRIM_HOP_LENGTH)
+        else:
+            bounds = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+            bounds[:, 1] = L if lengths is None else lengths.clamp(0, L)
+        peak = peak_abs(wavs, bounds)
+        out = torch.empty(B, L, device=dev)
+        quant = torch.empty(B, L, dtype=torch.int64, device=dev)
+        new_len = torch.empty(B, dtype=torch.int32, device=dev)
+        launch('ftmi_prepare_audio', f'prepare_audio[B={B},L={L}]', 0, 16.0 * B * L,
+               wavs.data_ptr(), wavs.stride(0), B, L, bounds.data_ptr(), peak.data_ptr(),
+               int(self.should_peak_norm), int(mu_law), bits, out.data_ptr(), out.stride(0),
+               quant.data_ptr(), quant.stride(0), new_len.data_ptr(), _stream())
+        plan = self.plan(dev)
+        frames = (1 + new_len // plan.hop).to(torch.int32)
+        mel = mel_spectrogram(plan, out, new_len, frames=frames)
+        return PreparedBatch(out, new_len, mel, frames, quant, bounds, peak)
+
+    def prepare_wav(self, y: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """One file's features, Preprocessor._convert_file without the pitch track:
+        numpy (L,) -> (mel float32 (n_mels, 1 + n // hop), quant int64 (n,)), n the samples
+        left after the trim."""
+        y = np.asarray(y)
+        if not np.issubdtype(y.dtype, np.floating) or y.ndim != 1:
+            raise ValueError('mono floating-point audio expected')
+        t = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).cuda()[None]
+        p = self.prepare_batch(t)
+        n = int(p.lengths[0])
+        if n < 1:
+            raise ValueError('nothing is left of the audio after the trim')
+        return (p.mel[0, :, :1 + n // self.hop_length].cpu().numpy(),
+                p.quant[0, :n].cpu().numpy())
 
     # -- utils/dsp.py:143-165 (vocoder label helpers) --
     @staticmethod

@@ -91,7 +91,9 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * ftmi_cross_entropy, ftmi_mol_loss and their *_workspace_bytes; ftmi_run_chain;
  * 21: ftmi_gemm_route, ftmi_conv1d_route, ftmi_conv_bank_route, ftmi_highway_route,
  * ftmi_gemm_switches_digest; no existing signature changed;
- * 22: ftmi_rnn_route, ftmi_rnn_switches_digest; no existing signature changed). */
+ * 22: ftmi_rnn_route, ftmi_rnn_switches_digest; no existing signature changed;
+ * added under 22 without a signature change: ftmi_frame_power, ftmi_trim_bounds, ftmi_peak_abs,
+ * ftmi_prepare_audio). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -1033,6 +1035,54 @@ int64_t ftmi_mol_loss_workspace_bytes(int64_t rows, int32_t K);
 int ftmi_mol_loss(const float *y_hat, int64_t ld, int64_t rows, int32_t channels, const float *y,
                   double num_classes, double log_scale_min, float *out, float *per_sample,
                   void *workspace, ftmi_stream_t stream);
+
+/* ---- Audio preparation (the reference's preprocess.py:51-91 Preprocessor._convert_file: the
+ * start / end silence trim of utils/dsp.py:112-113 -> librosa 0.7.2 effects.trim, the peak rule
+ * and the vocoder labels of utils/dsp.py:143-153; added under ABI 22 without a signature change) --
+ * Common: y fp32 audio rows (B, L), unit sample stride, row stride y_stride >= L in floats,
+ *   2 <= L < 2^31, B <= 65535 (more: FTMI_E_UNSUPPORTED).  lengths: device int32 [B] or NULL (L);
+ *   an entry is clamped into [0, L] on the device, so no value can address outside the row.  No
+ *   workgroup waits for another; every sum has a fixed order: the same input, the same bits.
+ * ftmi_frame_power: power[b][f] for f < F (F <= 1 + L / hop; the caller passes 1 + L / hop), fp32
+ *   (B, F) contiguous.  With yp = the item's L_b samples reflect-padded by frame_length / 2 on
+ *   both sides (numpy.pad mode='reflect', any pad width),
+ *     power[b][f] = (float)(sum_{i < frame_length} yp[f hop + i]^2 / frame_length)
+ *   summed in fp64 and rounded once (librosa's rms takes a float32 mean, its square root, and
+ *   squares again); frames f >= 1 + L_b / hop get 0.  frame_length even and > 0, hop >= 1, else
+ *   FTMI_E_ARG.  When hop divides frame_length (at most 64 times) each sample is squared once
+ *   into per-hop block sums and a frame adds frame_length / hop of them; otherwise each frame
+ *   is summed directly.
+ * ftmi_trim_bounds: per item, over its own frames f < 1 + L_b / hop, in fp64 from the fp32
+ *   powers:  db[f] = 10 log10(max(1e-10, power[f])) - 10 log10(max(1e-10, max_f power[f])),
+ *   a frame is non-silent when db[f] > -top_db;  bounds[b] = (first hop, min(L_b, (last + 1) hop))
+ *   over the non-silent frames, (0, 0) if there is none.  bounds: int32 (B, 2) contiguous.
+ * ftmi_peak_abs: peak[b] = max |y[b][i]| over bounds[b][0] <= i < bounds[b][1] (0 for an empty
+ *   range), exact.  Zeroes peak with a memset on the stream first.  bounds are clamped into
+ *   the row on the device.
+ * ftmi_prepare_audio: with (s, e) = bounds[b], n = e - s:
+ *     out[b][i]   = y[b][s + i] for i < n, divided by peak[b] (correctly rounded fp32 quotient)
+ *                   when (peak_norm || peak[b] > 1) && peak[b] > 0 — the reference divides an
+ *                   all-zero item by 0, here it stays as it is; 0 for n <= i < L
+ *     new_len[b]  = n
+ *     quant[b][i] (int64, optional: NULL skips the labels) for i < n, from out[b][i]:
+ *       mu_law != 0: floor((fx + 1) / 2 mu + 0.5), fx = sign(x) log(1 + mu |x|) / log(1 + mu),
+ *                    mu = 2^bits - 1, in fp64 from the fp32 sample (DSP.encode_mu_law)
+ *       mu_law == 0: trunc(clip((x + 1) * (2^bits - 1) / 2, 0, 2^bits - 1)), three separate fp32
+ *                    operations (DSP.float_2_label on float32 input); the MOL mode is bits = 16
+ *       0 for n <= i < L.
+ *   out (row stride out_stride >= L) must not alias y: rows move left.  bits outside 1..16:
+ *   FTMI_E_UNSUPPORTED. */
+int ftmi_frame_power(const float *y, int64_t y_stride, int32_t B, int64_t L, const int32_t *lengths,
+                     int32_t frame_length, int32_t hop, int32_t F, float *power,
+                     ftmi_stream_t stream);
+int ftmi_trim_bounds(const float *power, int32_t B, int32_t F, int64_t L, const int32_t *lengths,
+                     int32_t hop, double top_db, int32_t *bounds, ftmi_stream_t stream);
+int ftmi_peak_abs(const float *y, int64_t y_stride, int32_t B, int64_t L, const int32_t *bounds,
+                  float *peak, ftmi_stream_t stream);
+int ftmi_prepare_audio(const float *y, int64_t y_stride, int32_t B, int64_t L,
+                       const int32_t *bounds, const float *peak, int32_t peak_norm, int32_t mu_law,
+                       int32_t bits, float *out, int64_t out_stride, int64_t *quant,
+                       int64_t quant_stride, int32_t *new_len, ftmi_stream_t stream);
 
 #ifdef __cplusplus
 }
