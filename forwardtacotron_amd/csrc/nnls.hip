@@ -40,7 +40,8 @@ constexpr int NW = NT / 64;
 constexpr int CAP = 1024;       // breakpoints sorted per walk chunk
 constexpr int KCHUNK = 256;     // target chunk size
 constexpr int MC = 32;          // history columns whose small matrices the scalar parts stage in LDS
-constexpr int MMAX = 513;       // history columns at most (the reference's m = n_bins for n_fft 1024)
+constexpr int MMAX = 513;       // history columns at most (the reference's m = n_bins for n_fft 1024);
+                                // check_args rejects a larger m (dsp.NNLS_M_MAX is the same number)
 
 enum Phase { PH_DONE = 0, PH_EVAL = 1, PH_CAUCHY = 2, PH_WALK = 3, PH_FREEV = 4, PH_FORMK = 5,
              PH_SUBSM = 6, PH_BACKTRACK = 7 };
@@ -1928,7 +1929,8 @@ bool check_args(const ftmi_nnls_lbfgsb_args *p) {
   return p && p->mel && p->blocks && p->rowvals && p->rowptr && p->rowlo && p->bin_rows &&
          p->bin_w && p->pinv && p->workspace && p->S && p->active && p->B > 0 && p->F > 0 &&
          p->n_mels > 0 && p->n_mels <= 512 && p->n_bins > 0 && p->n_bins <= 2112 &&
-         p->n_blocks > 0 && p->groups > 0 && p->groups <= 64 && p->m > 0 && p->max_frames > 0;
+         p->n_blocks > 0 && p->groups > 0 && p->groups <= 64 && p->m > 0 && p->m <= MMAX &&
+         p->max_frames > 0;  // m <= MMAX: the scalar parts' LDS vectors hold 2 * MMAX entries
 }
 
 Args make_args(const ftmi_nnls_lbfgsb_args *p) {
@@ -1965,7 +1967,8 @@ Args make_args(const ftmi_nnls_lbfgsb_args *p) {
 
 extern "C" int64_t ftmi_nnls_lbfgsb_workspace_bytes(int32_t n_blocks, int32_t n_bins,
                                                     int32_t max_frames, int32_t m, int32_t groups) {
-  if (n_blocks <= 0 || n_bins <= 0 || max_frames <= 0 || m <= 0 || groups <= 0) return 0;
+  if (n_blocks <= 0 || n_bins <= 0 || max_frames <= 0 || m <= 0 || m > MMAX || groups <= 0)
+    return 0;
   const int64_t n_pad = ((int64_t)n_bins * max_frames + 255) & ~(int64_t)255;
   return (int64_t)n_blocks * carve(nullptr, n_pad, m, groups, nullptr);
 }

@@ -205,6 +205,7 @@ NNLS_METHODS = ('lbfgsb', 'fista')
 NNLS_GROUPS = 32  # workgroups per L-BFGS-B block (fixed: the sums, hence S, do not depend on
                   # how many blocks share a launch)
 NNLS_WS_CAP = 4 << 30  # workspace bytes per launch chunk
+NNLS_M_MAX = 513  # history columns at most (csrc/nnls.hip MMAX: its LDS vectors hold 2 * 513)
 
 
 def mel_to_stft(plan: DspPlan, mel: torch.Tensor, frames: Optional[torch.Tensor] = None,
@@ -214,7 +215,9 @@ def mel_to_stft(plan: DspPlan, mel: torch.Tensor, frames: Optional[torch.Tensor]
 
     method 'lbfgsb' (default) runs the reference's own NNLS on the device — util.nnls'
     L-BFGS-B over 127-frame blocks, same iterates to rounding (ftmi_nnls_lbfgsb_*) — so S is
-    the reference's S.  'fista' is the fast per-frame solver (`iters` FISTA steps, default
+    the reference's S.  The history holds at most NNLS_M_MAX = 513 updates: a block that needs
+    more (possible only at n_fft 2048 / 4096, on mels far from speech) raises RuntimeError
+    (status 4).  'fista' is the fast per-frame solver (`iters` FISTA steps, default
     32): a
     minimiser of the same objective, but the minimiser is not unique, so its S (and the
     Griffin-Lim wav built on it) is NOT the reference's (tests/test_gpu_dsp.py states by how
@@ -290,10 +293,12 @@ def _nnls_lbfgsb(plan: DspPlan, mel: torch.Tensor, frames: Optional[torch.Tensor
         launch('ftmi_nnls_lbfgsb_finish', f'nnls_lbfgsb_finish[blocks={nblk}]', 0, 0, ap,
                _p(fr_dev), status.data_ptr(), inf.data_ptr(), stream)
         st = status.cpu().tolist()
-        if st[0] & 4 and m < plan.nb:
+        if st[0] & 4 and m < min(plan.nb, NNLS_M_MAX):
             # history full (more than 32 updates: the synthetic-weights mels of the tests take
-            # ~150): rerun the chunk with the reference's whole history, m = n_bins
-            m = plan.nb
+            # ~150): rerun the chunk with the reference's whole history, m = n_bins, capped at
+            # NNLS_M_MAX columns (n_fft 2048 / 4096: up to 513 updates the reference's history
+            # of n_bins columns has not wrapped either; a block that needs more raises below)
+            m = min(plan.nb, NNLS_M_MAX)
             continue
         if st[0] and debug is None:
             raise RuntimeError(f'L-BFGS-B NNLS failed (status {st[0]}: 2 abnormal line search, '
