@@ -21,6 +21,9 @@ _lib = None
 
 c_int, c_int64, c_float, c_void_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 P = c_void_p  # every device pointer travels as void*
+# 22 still: ftmi_wavernn_packed and ftmi_wr_unfold_packed are new symbols; no existing signature
+# or struct changed, so a caller built against the earlier 22 keeps working (the version is
+# bumped on a signature change, include/ftmi.h)
 ABI_VERSION = 22
 MMA_F32, MMA_BF16X6, MMA_F16X3 = 0, 1, 2
 
@@ -70,6 +73,21 @@ class WaveRNNArgs(ctypes.Structure):
         ('seed', ctypes.c_uint64)] + [(n, c_int) for n in (
             'bias_row', 'item_rows', 'frames_per_item', 'hop', 'fold_stride', 'batched', 'B', 'L',
             'n_classes', 'mol', 'rnn_dims', 'fc_dims', 'feat_dims', 'aux_dims')]
+
+
+class WaveRNNPackedArgs(ctypes.Structure):
+    """Mirror of ftmi_wavernn_packed_args (include/ftmi.h)."""
+    _fields_ = [(n, P) for n in ('w_hh1', 'w_hh2', 'w_ih2a', 'w_fc1a', 'w_fc2a', 'w_fc3', 'b_fc3',
+                                 'b_hh1', 'b_hh2', 'u1', 'u2', 'v1', 'wm', 'cond', 'mel', 'xin',
+                                 'samples', 'logits', 'workspace', 'status', 'folds',
+                                 'launch_steps')] + [(n, c_int) for n in (
+                                     'n_folds', 'L', 'n_out_rows', 'n_mel_rows', 'bias_row', 'hop',
+                                     'n_classes', 'mol', 'rnn_dims', 'fc_dims', 'feat_dims', 'aux_dims')]
+
+
+# columns of an ftmi_wr_fold row / an ftmi_wr_item row as int32 (k0, k1: the uint32 bit patterns)
+WR_FOLD_COLS = ('mel_row0', 'cond_row0', 'g0', 'n_rows', 'philox_b', 'out_row', 'k0', 'k1')
+WR_ITEM_COLS = ('first_row', 'n_folds', 'wave_len', 'out_offset')
 
 
 class TacoArgs(ctypes.Structure):
@@ -198,6 +216,9 @@ SIGNATURES = {
     'ftmi_wavernn': (c_int, [ctypes.POINTER(WaveRNNArgs), P]),
     'ftmi_set_wavernn_spin_limit': (ctypes.c_uint32, [ctypes.c_uint32]),
     'ftmi_wr_unfold': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'ftmi_wavernn_packed': (c_int, [ctypes.POINTER(WaveRNNPackedArgs), P]),
+    'ftmi_wr_unfold_packed': (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, P, c_int64, P]),
     'ftmi_tacotron_decoder_workspace_bytes': (c_int64, [c_int, c_int]),
     'ftmi_tacotron_decoder': (c_int, [ctypes.POINTER(TacoArgs), P]),
     'ftmi_align_workspace_bytes': (c_int64, [c_int, c_int, c_int]),

@@ -5,8 +5,11 @@
 //                            UpsampleNetwork.up_layers pair (:74-81, :88), on time-major rows
 //   wavernn_kernel           the sample loop of WaveRNN.generate (:203-241) — or, teacher-
 //                            forced, WaveRNN.forward (:145-169) — as ONE persistent launch
+//                            (third template parameter PK: the packed form, each fold described
+//                            by an ftmi_wr_fold row — the folds of many utterances in one launch)
 //   wr_unfold_kernel         generate's tail (:246-261): mu-law decode, xfade_and_unfold
 //                            (:343-406), crop, 20-hop fade-out; float64 like the reference
+//   wr_unfold_packed_kernel  the same tail for every utterance of a packed sample matrix
 //
 // The sample loop.  Per step t and fold b the reference computes
 //   x = I([s_{t-1}, m_t, a1_t]);  h1 = GRU1(x, h1);  x += h1;  h2 = GRU2([x, a2_t], h2);
@@ -152,6 +155,29 @@ struct WrParams {
   unsigned spin_limit;
 };
 
+// Packed launches (ftmi_wavernn_packed): fold b of the launch is row fold0 + b of a table of
+// ftmi_wr_fold descriptors in global memory: where it reads its conditioning, which Philox
+// counter word and key it draws with, which output row it writes.  The table rows of an
+// instance are copied to LDS once, before the loop.  ldo: row stride of xin / samples /
+// logits (L is the launch's step count).
+struct WrParamsPk : WrParams {
+  const ftmi_wr_fold *folds;
+  int ldo;
+};
+template <bool PK>
+struct WrPSel {
+  typedef WrParams type;
+};
+template <>
+struct WrPSel<true> {
+  typedef WrParamsPk type;
+};
+template <int NBV>
+__device__ __forceinline__ ftmi_wr_fold *fold_table() {
+  __shared__ __attribute__((aligned(16))) ftmi_wr_fold fd[NBV];
+  return fd;
+}
+
 __device__ __forceinline__ void report_timeout(const WrParams &p) {
   __hip_atomic_store(p.ws, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (p.status) atomicOr(p.status, STATUS_TIMEOUT);
@@ -162,7 +188,20 @@ struct Pos {
   int mel_row;    // -1: padded (zero) position
   int cond_row;
 };
-__device__ __forceinline__ Pos position(const WrParams &p, int b, int t) {
+template <bool PK, class P>
+__device__ __forceinline__ Pos position(const P &p, const ftmi_wr_fold *fd, int b, int t) {
+  if constexpr (PK) {
+    const int g = fd[b].g0 + t;
+    Pos r;
+    if (t < p.L && g < fd[b].n_rows) {
+      r.mel_row = fd[b].mel_row0 + g;
+      r.cond_row = fd[b].cond_row0 + g / p.hop;
+    } else {
+      r.mel_row = -1;
+      r.cond_row = p.bias_row;
+    }
+    return r;
+  }
   const int fb = p.fold0 + b;
   const int g = p.batched ? fb * p.fold_stride + t : t;
   const int item = p.batched ? 0 : fb;
@@ -175,6 +214,28 @@ __device__ __forceinline__ Pos position(const WrParams &p, int b, int t) {
     r.cond_row = p.bias_row;
   }
   return r;
+}
+// what identifies fold b outside the launch: its row of xin / samples / logits (in
+// elements), its Philox counter word and key
+template <bool PK, class P>
+__device__ __forceinline__ size_t out_base(const P &p, const ftmi_wr_fold *fd, int b) {
+  if constexpr (PK) return (size_t)fd[b].out_row * p.ldo;
+  else return (size_t)(p.fold0 + b) * p.L;
+}
+template <bool PK, class P>
+__device__ __forceinline__ unsigned fold_word(const P &p, const ftmi_wr_fold *fd, int b) {
+  if constexpr (PK) return (unsigned)fd[b].philox_b;
+  else return (unsigned)(p.fold0 + b);
+}
+template <bool PK, class P>
+__device__ __forceinline__ unsigned key0(const P &p, const ftmi_wr_fold *fd, int b) {
+  if constexpr (PK) return fd[b].k0;
+  else return p.k0;
+}
+template <bool PK, class P>
+__device__ __forceinline__ unsigned key1(const P &p, const ftmi_wr_fold *fd, int b) {
+  if constexpr (PK) return fd[b].k1;
+  else return p.k1;
 }
 
 // Geometry of one instance (a replica of the weight-distributed pipeline over its own
@@ -284,8 +345,9 @@ __device__ __forceinline__ void publish_z(const WrParams &p, int t, int b, int f
 // best Gumbel score and its class), MOL the NC logits.  8 threads per fold, each with its
 // (up to 8) 16-byte granule pairs requested at once.  On a timeout the abort flag is set
 // (visible after the internal barrier).
-template <int NBV, int NI>
-__device__ __forceinline__ void acquire_sample(const WrParams &p, WrShared<NBV, NI> &sh, int t, bool store) {
+template <int NBV, int NI, bool PK, class P>
+__device__ __forceinline__ void acquire_sample(const P &p, const ftmi_wr_fold *fd, WrShared<NBV, NI> &sh, int t,
+                                               bool store) {
   const int tid = threadIdx.x;
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(p.xch, (short)0, 0x7FFFFFF0, 0x00020000);
   const unsigned want = step_tag(t);
@@ -368,13 +430,14 @@ __device__ __forceinline__ void acquire_sample(const WrParams &p, WrShared<NBV, 
       int am = 0;
       float bt = -INFINITY;
       for (int k = 0; k < nr; ++k) {
-        const u32x4 w = philox((u32x4){(unsigned)t, (unsigned)(p.fold0 + tid), (unsigned)(k >> 2), 1u},
-                               p.k0, p.k1);
+        const u32x4 w = philox((u32x4){(unsigned)t, fold_word<PK>(p, fd, tid), (unsigned)(k >> 2), 1u},
+                               key0<PK>(p, fd, tid), key1<PK>(p, fd, tid));
         const float u = 1e-5f + u01(pword(w, k & 3)) * (1.0f - 2e-5f);
         const float tv = l[k] - logf(-logf(u));
         if (tv > bt) bt = tv, am = k;
       }
-      const u32x4 w2 = philox((u32x4){(unsigned)t, (unsigned)(p.fold0 + tid), 0u, 2u}, p.k0, p.k1);
+      const u32x4 w2 = philox((u32x4){(unsigned)t, fold_word<PK>(p, fd, tid), 0u, 2u},
+                              key0<PK>(p, fd, tid), key1<PK>(p, fd, tid));
       const float u = 1e-5f + u01(w2.x) * (1.0f - 2e-5f);
       const float mean = l[nr + am];
       const float ls = fmaxf(l[2 * nr + am], -32.23619130191664f);  // log(1e-14), fp32
@@ -385,24 +448,25 @@ __device__ __forceinline__ void acquire_sample(const WrParams &p, WrShared<NBV, 
     }
     __syncthreads();
   }
-  if (store && tid < p.B && p.samples) p.samples[(size_t)(p.fold0 + tid) * p.L + t] = sh.sval[tid];
+  if (store && tid < p.B && p.samples) p.samples[out_base<PK>(p, fd, tid) + t] = sh.sval[tid];
 }
 
 // this step's mel rows, fetched one step ahead into registers (the global-load latency
 // hides behind a whole step) and stored to LDS at the top of the step
-template <int NBV, int NI>
+template <int NBV, int NI, bool PK>
 struct MelPrefetch {
   static constexpr int NT = Geo<NI>::NT;
   static constexpr int N = (NBV * (WR_NM / 4) + NT - 1) / NT;
   f32x4 r[N];
-  __device__ __forceinline__ void fetch(const WrParams &p, int t) {
+  template <class P>
+  __device__ __forceinline__ void fetch(const P &p, const ftmi_wr_fold *fd, int t) {
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       const int f = threadIdx.x + i * NT;
       const int b = f / (WR_NM / 4), c = (f % (WR_NM / 4)) * 4;
       r[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (f < NBV * (WR_NM / 4) && b < p.B) {
-        const Pos ps = position(p, b, t);
+        const Pos ps = position<PK>(p, fd, b, t);
         if (ps.mel_row >= 0) r[i] = *(const f32x4 *)&p.mel[(size_t)ps.mel_row * WR_NM + c];
       }
     }
@@ -512,8 +576,9 @@ __device__ __forceinline__ void matvec_mel(const float (&w)[10], const float *me
   }
 }
 
-template <int NBV, int NI>
-__global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams p0) {
+template <int NBV, int NI, bool PK = false>
+__global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const typename WrPSel<PK>::type p0) {
+  typedef typename WrPSel<PK>::type P;
   using G = Geo<NI>;
   constexpr int NT = G::NT, UG = G::UG, FR = G::FR, NG = G::NG;
   __shared__ WrShared<NBV, NI> sh;
@@ -521,12 +586,20 @@ __global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams 
   const int s = tid >> 3, kl = tid & 7;
   // this workgroup's instance: its folds and exchange buffers
   const int inst = blockIdx.x / G::W, local = blockIdx.x % G::W;
-  WrParams p = p0;
+  P p = p0;
   {
     const int bi = (p0.B + NI - 1) / NI;
     p.fold0 = p0.fold0 + inst * bi;
     p.B = p0.B - inst * bi < bi ? p0.B - inst * bi : bi;
     p.xch = p0.xch + (size_t)inst * (4 * XS_VEC + XS_Z);
+  }
+  // packed: this instance's descriptors (table rows fold0 .. fold0 + B), visible after the
+  // barrier that ends the prologue
+  const ftmi_wr_fold *fd = nullptr;
+  if constexpr (PK) {
+    ftmi_wr_fold *tab = fold_table<NBV>();
+    if (tid < p.B) tab[tid] = p.folds[p.fold0 + tid];
+    fd = tab;
   }
   // diag (FTMI_WR_STAMPS=1): thread 0 of instance 0's first GRU and first FC workgroup sum
   // s_memtime deltas per phase into the workspace (timing only; outputs unchanged)
@@ -620,7 +693,7 @@ __global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams 
     float gn[3] = {0.f, 0.f, 0.f}, qn[3] = {0.f, 0.f, 0.f};
     auto fetch_cond = [&](int t) {
       if (cell) {
-        const Pos ps = position(p, cb, t);
+        const Pos ps = position<PK>(p, fd, cb, t);
         const float *crow = p.cond + (size_t)ps.cond_row * WR_COND;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -629,8 +702,8 @@ __global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams 
         }
       }
     };
-    MelPrefetch<NBV, NI> mp;
-    mp.fetch(p, 0);
+    MelPrefetch<NBV, NI, PK> mp;
+    mp.fetch(p, fd, 0);
     fetch_cond(0);
 
     for (int t = 0; t < p.L; ++t) {
@@ -640,7 +713,7 @@ __global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams 
       for (int q = 0; q < 3; ++q) gc[q] = gn[q], qc[q] = qn[q];
       mp.store(sh);
       if (t + 1 < p.L) {
-        mp.fetch(p, t + 1);
+        mp.fetch(p, fd, t + 1);
         fetch_cond(t + 1);
       }
       if constexpr (WL)  // W_hh1 h1_{t-1}
@@ -661,8 +734,8 @@ __global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams 
       // ---- the chain: s_{t-1} -------------------------------------------------------
       __syncthreads();
       WR_STAMP(2);
-      if (t > 0) acquire_sample(p, sh, t - 1, !p.xin && local == 0);  // teacher-forced: pace only
-      if (p.xin && tid < p.B) sh.sval[tid] = p.xin[(size_t)(p.fold0 + tid) * p.L + t];
+      if (t > 0) acquire_sample<NBV, NI, PK>(p, fd, sh, t - 1, !p.xin && local == 0);  // teacher-forced: pace only
+      if (p.xin && tid < p.B) sh.sval[tid] = p.xin[out_base<PK>(p, fd, tid) + t];
       __syncthreads();
       WR_STAMP(3);
       if (sh.abort_flag) return;
@@ -709,7 +782,7 @@ __global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams 
     }
     if (!p.xin && local == 0) {  // the last sample
       __syncthreads();
-      acquire_sample(p, sh, p.L - 1, true);
+      acquire_sample<NBV, NI, PK>(p, fd, sh, p.L - 1, true);
     }
   } else {
     // ================================= FC workgroup =====================================
@@ -758,32 +831,32 @@ __global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams 
     float rn = 0.f, sn = 0.f;
     auto fetch_cond = [&](int t) {
       if (cell) {
-        const Pos ps = position(p, cb, t);
+        const Pos ps = position<PK>(p, fd, cb, t);
         rn = p.cond[(size_t)ps.cond_row * WR_COND + 6 * WR_R + r0 + cr];
       }
       if (cell2) {
-        const Pos ps = position(p, cb2, t);
+        const Pos ps = position<PK>(p, fd, cb2, t);
         sn = p.cond[(size_t)ps.cond_row * WR_COND + 6 * WR_R + WR_F + q0 + cr2];
       }
     };
-    MelPrefetch<NBV, NI> mp;
-    mp.fetch(p, 0);
+    MelPrefetch<NBV, NI, PK> mp;
+    mp.fetch(p, fd, 0);
     fetch_cond(0);
 
     for (int t = 0; t < p.L; ++t) {
       const float rc = rn, sc = sn;
       mp.store(sh);
       if (t + 1 < p.L) {
-        mp.fetch(p, t + 1);
+        mp.fetch(p, fd, t + 1);
         fetch_cond(t + 1);
       }
       __syncthreads();
       matvec_mel(wmr, sh.melv, kl, sh.partm[s], actm, p.B);
       WR_STAMP(0);
       // ---- s_{t-1} -------------------------------------------------------------------
-      if (t > 0) acquire_sample(p, sh, t - 1, false);
+      if (t > 0) acquire_sample<NBV, NI, PK>(p, fd, sh, t - 1, false);
       WR_STAMP(1);
-      if (p.xin && tid < p.B) sh.sval[tid] = p.xin[(size_t)(p.fold0 + tid) * p.L + t];
+      if (p.xin && tid < p.B) sh.sval[tid] = p.xin[out_base<PK>(p, fd, tid) + t];
       // ---- h1_t + h2_t ----------------------------------------------------------------
       acquire_vec(p, sh, 0, t, false);
       __syncthreads();
@@ -835,12 +908,12 @@ __global__ __launch_bounds__(Geo<NI>::NT, 1) void wavernn_kernel(const WrParams 
 #pragma unroll
             for (int i = 1; i < 4; ++i) l += sh.part[2][rr * 4 + i][b];
             l = l + p.b_fc3[k];
-            if (p.logits) p.logits[((size_t)(p.fold0 + b) * p.L + t) * p.NC + k] = l;
+            if (p.logits) p.logits[(out_base<PK>(p, fd, b) + t) * p.NC + k] = l;
             if (p.mol) {
               publish_z(p, t, b, k, l, k);  // MOL: every logit is a granule of its own
             } else {
-              const u32x4 w = philox((u32x4){(unsigned)t, (unsigned)(p.fold0 + b), (unsigned)(k >> 2), 0u},
-                                     p.k0, p.k1);
+              const u32x4 w = philox((u32x4){(unsigned)t, fold_word<PK>(p, fd, b), (unsigned)(k >> 2), 0u},
+                                     key0<PK>(p, fd, b), key1<PK>(p, fd, b));
               z = l - logf(-logf(u01(pword(w, k & 3))));
             }
           }
@@ -906,11 +979,10 @@ __device__ __forceinline__ double mu_decode(double y, int mu_law, int n_classes)
   return sg / mu * (exp2(bits * fabs(y)) - 1.0);
 }
 
-__global__ void wr_unfold_kernel(const float *smp, int B, int L, int target, int overlap,
-                                 int batched, int mu_law, int n_classes, int wave_len, int nf,
-                                 double *out) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= wave_len) return;
+// sample j < wave_len of one utterance's wave from its B fold rows (both unfold kernels)
+__device__ __forceinline__ double wr_unfold_value(const float *smp, int B, int L, int target, int overlap,
+                                                  int batched, int mu_law, int n_classes, int wave_len,
+                                                  int nf, int j) {
   double v;
   if (batched) {
     const int stride = target + overlap;
@@ -938,7 +1010,28 @@ __global__ void wr_unfold_kernel(const float *smp, int B, int L, int target, int
     v = mu_decode((double)smp[j], mu_law, n_classes);
   }
   if (nf > 0 && j >= wave_len - nf) v = v * np_linspace(1.0, 0.0, nf, j - (wave_len - nf));
-  out[j] = v;
+  return v;
+}
+
+__global__ void wr_unfold_kernel(const float *smp, int B, int L, int target, int overlap,
+                                 int batched, int mu_law, int n_classes, int wave_len, int nf,
+                                 double *out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= wave_len) return;
+  out[j] = wr_unfold_value(smp, B, L, target, overlap, batched, mu_law, n_classes, wave_len, nf, j);
+}
+
+// every utterance of a packed sample matrix in one launch: blockIdx.y = the item, its
+// fold rows from first_row on, its wave at out + out_offset
+__global__ void wr_unfold_packed_kernel(const float *smp, int L, const ftmi_wr_item *items, int target,
+                                        int overlap, int batched, int mu_law, int n_classes, int nf,
+                                        double *out) {
+  const ftmi_wr_item it = items[blockIdx.y];
+  const float *rows = smp + (size_t)it.first_row * L;
+  double *dst = out + it.out_offset;
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < it.wave_len; j += gridDim.x * blockDim.x)
+    dst[j] = wr_unfold_value(rows, it.n_folds, L, target, overlap, batched, mu_law, n_classes,
+                             it.wave_len, nf, j);
 }
 
 unsigned g_wr_spin = SPIN_DEFAULT;
@@ -1041,6 +1134,132 @@ extern "C" int ftmi_wavernn(const ftmi_wavernn_args *a, ftmi_stream_t stream) {
   return FTMI_OK;
 }
 
+namespace {
+
+// A descriptor table handed to a packed entry point.  Device memory is used as it is (its
+// rows were checked by whoever filled it: the binding); anything else is host memory, which
+// the entry point reads to check every row and then stages in stream order.
+bool table_on_device(const void *tbl) {
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, tbl) != hipSuccess) {
+    (void)hipGetLastError();  // an unregistered host pointer: not an error of the caller's
+    return false;
+  }
+  return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+struct StagedTable {
+  void *dev = nullptr;
+  hipStream_t s = nullptr;
+  int stage(const void *host, size_t bytes, hipStream_t stream) {
+    s = stream;
+    hipError_t e = hipMallocAsync(&dev, bytes, s);
+    if (e != hipSuccess) {
+      dev = nullptr;
+      return (int)e;
+    }
+    e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s);
+    return e == hipSuccess ? FTMI_OK : (int)e;
+  }
+  ~StagedTable() {
+    if (dev) (void)hipFreeAsync(dev, s);
+  }
+};
+
+int check_fold(const ftmi_wr_fold &f, const ftmi_wavernn_packed_args *a) {
+  if (f.g0 < 0 || f.n_rows <= 0 || f.g0 >= f.n_rows || f.g0 > INT32_MAX - a->L) return FTMI_E_SHAPE;
+  if (f.out_row < 0 || f.out_row >= a->n_out_rows || f.philox_b < 0) return FTMI_E_SHAPE;
+  if (f.mel_row0 < 0 || (int64_t)f.mel_row0 + f.n_rows > a->n_mel_rows) return FTMI_E_SHAPE;
+  // the last frame a real position reads is below the bias row
+  if (f.cond_row0 < 0 || (int64_t)f.cond_row0 + (f.n_rows - 1) / a->hop >= a->bias_row) return FTMI_E_SHAPE;
+  return FTMI_OK;
+}
+
+}  // namespace
+
+extern "C" int ftmi_wavernn_packed(const ftmi_wavernn_packed_args *a, ftmi_stream_t stream) {
+  if (!a) return FTMI_E_ARG;
+  if (!a->w_hh1 || !a->w_hh2 || !a->w_ih2a || !a->w_fc1a || !a->w_fc2a || !a->w_fc3 ||
+      !a->b_fc3 || !a->b_hh1 || !a->b_hh2 || !a->u1 || !a->u2 || !a->v1 || !a->wm || !a->cond ||
+      !a->mel || !a->workspace || !a->folds)
+    return FTMI_E_ARG;
+  if (a->n_folds <= 0 || a->L <= 0 || a->hop <= 0 || a->n_out_rows <= 0 || a->n_mel_rows <= 0 ||
+      a->bias_row <= 0)
+    return FTMI_E_ARG;
+  if (a->rnn_dims != WR_R || a->fc_dims != WR_F || a->feat_dims != WR_NM || a->aux_dims != WR_NA)
+    return FTMI_E_UNSUPPORTED;
+  if (a->mol ? a->n_classes != 30
+             : (a->n_classes < 2 || a->n_classes > WR_F || (a->n_classes & (a->n_classes - 1)) != 0))
+    return FTMI_E_UNSUPPORTED;
+  if (a->xin ? !a->logits : !a->samples) return FTMI_E_ARG;
+  if (!ftmi_aligned16(a->mel) || !ftmi_aligned16(a->workspace) || !ftmi_aligned16(a->folds))
+    return FTMI_E_ALIGN;
+  const int n_launches = (a->n_folds + WR_NBMAX - 1) / WR_NBMAX;
+  for (int i = 0; a->launch_steps && i < n_launches; ++i)
+    if (a->launch_steps[i] <= 0 || a->launch_steps[i] > a->L) return FTMI_E_SHAPE;
+  const bool on_device = table_on_device(a->folds);
+  if (!on_device)
+    for (int i = 0; i < a->n_folds; ++i)
+      if (int rc = check_fold(a->folds[i], a)) return rc;
+  if (cu_count() < WR_GRID) return FTMI_E_UNSUPPORTED;
+  hipStream_t s = ftmi_hs(stream);
+  StagedTable staged;
+  if (!on_device)
+    if (int rc = staged.stage(a->folds, (size_t)a->n_folds * sizeof(ftmi_wr_fold), s)) return rc;
+  WrParamsPk p{};
+  p.w_hh1 = a->w_hh1, p.w_hh2 = a->w_hh2, p.w_ih2a = a->w_ih2a;
+  p.w_fc1a = a->w_fc1a, p.w_fc2a = a->w_fc2a, p.w_fc3 = a->w_fc3, p.b_fc3 = a->b_fc3;
+  p.b_hh1 = a->b_hh1, p.b_hh2 = a->b_hh2, p.u1 = a->u1, p.u2 = a->u2, p.v1 = a->v1;
+  p.wm = a->wm, p.cond = a->cond, p.mel = a->mel;
+  p.bias_row = a->bias_row, p.hop = a->hop;
+  p.xin = a->xin, p.samples = a->samples, p.logits = a->logits;
+  unsigned *ws = (unsigned *)a->workspace;
+  p.ws = ws;
+  p.xch = (float *)(ws + WS_CTRL);
+  p.status = a->status;
+  p.NC = a->n_classes, p.mol = a->mol;
+  p.spin_limit = g_wr_spin;
+  p.folds = on_device ? a->folds : (const ftmi_wr_fold *)staged.dev;
+  p.ldo = a->L;
+  static const int stamps_env = [] {
+    const char *v = getenv("FTMI_WR_STAMPS");
+    return v ? atoi(v) : 0;
+  }();
+  p.stamps = stamps_env;
+  static const int ni_env = [] {  // FTMI_WR_NI=1 forces one instance, as in ftmi_wavernn
+    const char *v = getenv("FTMI_WR_NI");
+    return v ? atoi(v) : 2;
+  }();
+  // ftmi_wavernn's host loop over the table: <= WR_NBMAX folds per launch in table order, two
+  // instances from two folds on, the same NBV choice, the residency check before each launch
+  for (int f0 = 0, li = 0; f0 < a->n_folds; f0 += p.B, ++li) {
+    p.fold0 = f0;
+    p.B = a->n_folds - f0 < WR_NBMAX ? a->n_folds - f0 : WR_NBMAX;
+    p.L = a->launch_steps ? a->launch_steps[li] : a->L;
+    const int ni = (p.B >= 2 && ni_env != 1) ? 2 : 1;
+    const int bi = (p.B + ni - 1) / ni;
+    hipError_t e = hipMemsetAsync(a->workspace, 0, (size_t)ftmi_wavernn_workspace_bytes(), s);
+    if (e != hipSuccess) return (int)e;
+#define FTMI_WR_LAUNCH(NBV_, NI_)                                                                  \
+  do {                                                                                             \
+    if (int rc = ftmi_resident_ok((const void *)wavernn_kernel<NBV_, NI_, true>, WR_GRID, WR_NT * NI_, 0)) \
+      return rc;                                                                                   \
+    hipLaunchKernelGGL((wavernn_kernel<NBV_, NI_, true>), dim3(WR_GRID), dim3(WR_NT * NI_), 0, s, p); \
+  } while (0)
+    if (ni == 1) {
+      if (p.B <= 8) FTMI_WR_LAUNCH(8, 1);
+      else if (p.B <= 16) FTMI_WR_LAUNCH(16, 1);
+      else FTMI_WR_LAUNCH(32, 1);
+    } else {
+      if (bi <= 8) FTMI_WR_LAUNCH(8, 2);
+      else FTMI_WR_LAUNCH(16, 2);
+    }
+#undef FTMI_WR_LAUNCH
+    FTMI_CHECK_LAUNCH();
+  }
+  return FTMI_OK;
+}
+
 extern "C" int ftmi_wr_stretch_conv(const float *x, int64_t x_batch_stride, int32_t B, int32_t W,
                                     int32_t C, int32_t scale, const float *w, float *y,
                                     int64_t y_batch_stride, int32_t W_out, int32_t crop0,
@@ -1069,6 +1288,39 @@ extern "C" int ftmi_wr_unfold(const float *samples, int32_t B, int32_t L, int32_
     return FTMI_E_SHAPE;
   hipLaunchKernelGGL(wr_unfold_kernel, dim3((wave_len + 255) / 256), dim3(256), 0, ftmi_hs(stream),
                      samples, B, L, target, overlap, batched, mu_law, n_classes, wave_len, fade_len, out);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_wr_unfold_packed(const float *samples, int32_t n_rows, int32_t L,
+                                     const ftmi_wr_item *items, int32_t n_items, int32_t target,
+                                     int32_t overlap, int32_t batched, int32_t mu_law,
+                                     int32_t n_classes, int32_t fade_len, double *out, int64_t out_len,
+                                     ftmi_stream_t stream) {
+  if (!samples || !out || !items) return FTMI_E_ARG;
+  if (n_rows <= 0 || L <= 0 || n_items <= 0 || fade_len < 0 || n_classes < 2 || out_len <= 0)
+    return FTMI_E_ARG;
+  if (mu_law && (n_classes & (n_classes - 1)) != 0) return FTMI_E_UNSUPPORTED;
+  if (batched && (target < 0 || overlap < 0 || L != target + 2 * overlap)) return FTMI_E_SHAPE;
+  if (n_items > 65535 || out_len > ((int64_t)1 << 30)) return FTMI_E_UNSUPPORTED;  // grid y; int32 offsets
+  if (!ftmi_aligned16(items)) return FTMI_E_ALIGN;
+  const bool on_device = table_on_device(items);
+  for (int i = 0; !on_device && i < n_items; ++i) {  // ftmi_wr_unfold's rules, per item
+    const ftmi_wr_item &it = items[i];
+    if (it.first_row < 0 || it.n_folds <= 0 || (int64_t)it.first_row + it.n_folds > n_rows) return FTMI_E_SHAPE;
+    if (it.wave_len <= 0 || it.wave_len < fade_len) return FTMI_E_SHAPE;
+    if (batched ? (int64_t)it.wave_len > (int64_t)it.n_folds * (target + overlap) + overlap
+                : (it.n_folds != 1 || it.wave_len > L))
+      return FTMI_E_SHAPE;
+    if (it.out_offset < 0 || (int64_t)it.out_offset + it.wave_len > out_len) return FTMI_E_SHAPE;
+  }
+  hipStream_t s = ftmi_hs(stream);
+  StagedTable staged;
+  if (!on_device)
+    if (int rc = staged.stage(items, (size_t)n_items * sizeof(ftmi_wr_item), s)) return rc;
+  const ftmi_wr_item *tbl = on_device ? items : (const ftmi_wr_item *)staged.dev;
+  hipLaunchKernelGGL(wr_unfold_packed_kernel, dim3(128, n_items), dim3(256), 0, s, samples, L, tbl,
+                     target, overlap, batched, mu_law, n_classes, fade_len, out);
   FTMI_CHECK_LAUNCH();
   return FTMI_OK;
 }

@@ -6,7 +6,9 @@ phonemizer — is absent from this image, so raw English text is refused with th
         [--input_phonemes "həloʊ wɜːld" | --input_tokens 12,40,7 | --sentences file] \\
         [--alpha 1.0] [--amp 1.0] {griffinlim,melgan,hifigan,wavernn}
     python -m forwardtacotron_amd.gen_forward ... wavernn \\
-        [--voc_checkpoint voc.pt | --voc_synthetic] [--target 11000] [--overlap 550]
+        [--voc_checkpoint voc.pt | --voc_synthetic] [--target 11000] [--overlap 550] \\
+        [--voc_batch N]   (N > 1: up to N sentences' mels vocoded by one
+                           WaveRNN.generate_batch call; the same file names)
 
 Without --checkpoint the checkpoint is found from --config like the reference
 (`gen_forward.py:68-72`: checkpoints/{tts_model_id}.forward/latest_model.pt).
@@ -200,6 +202,9 @@ def build_parser() -> argparse.ArgumentParser:
     wr_parser.add_argument('--voc_checkpoint', type=str,
                            help='[string/path] Load in different WaveRNN weights')
     wr_parser.add_argument('--voc_synthetic', action='store_true', help='synthetic WaveRNN weights')
+    wr_parser.add_argument('--voc_batch', default=1, type=int,
+                           help='[int] sentences vocoded together: their folds share WaveRNN '
+                                'launches (WaveRNN.generate_batch); 1: one sentence at a time')
     for name in ('griffinlim', 'melgan', 'hifigan'):
         subparsers.add_parser(name)
     return parser
@@ -244,12 +249,32 @@ def main(argv: Optional[Sequence[str]] = None) -> List[Path]:
     from .host_io import PinnedD2H
     d2h = PinnedD2H(device, depth=1)  # pinned D2H: the drop-in for .cpu() (gen_forward.py:120)
     written = []
+    voc_batch = getattr(args, 'voc_batch', 1) if args.vocoder == 'wavernn' else 1
+    if voc_batch < 1:
+        raise SystemExit('--voc_batch must be at least 1')
+    pending = []  # --voc_batch > 1: (name, mel_post on the device) still to be vocoded
+
+    def flush():
+        voc_model, voc_dsp = voc
+        waves = voc_model.generate_batch([m for _, m in pending], batched=True, target=args.target,
+                                         overlap=args.overlap, mu_law=voc_dsp.mu_law)
+        for (name, _), wav in zip(pending, waves):
+            p = out_path / f'{name}.wav'
+            dsp.save_wav(wav, p)
+            written.append(p)
+        pending.clear()
+
     for i, ids in enumerate(texts, 1):
         print(f'\n| Generating {i}/{len(texts)}')
         x = torch.as_tensor(ids, dtype=torch.long, device=device).unsqueeze(0)
         name = wav_name(i, tts_k, args.alpha, args.amp, args.vocoder)
         gen = tts_model.generate(x=x, alpha=args.alpha, pitch_function=pitch_function,
                                  energy_function=energy_function)
+        if voc_batch > 1:  # the next generate may reuse the buffer mel_post lives in
+            pending.append((name, gen['mel_post'].clone()))
+            if len(pending) == voc_batch or i == len(texts):
+                flush()
+            continue
         m = d2h.fetch(gen['mel_post'])
         written.append(write_output(m, name, args.vocoder, out_path, dsp, voc,
                                     getattr(args, 'target', 11000), getattr(args, 'overlap', 550),

@@ -1012,6 +1012,77 @@ def wr_unfold(samples: torch.Tensor, target: int, overlap: int, batched: bool, m
     return out
 
 
+def check_wr_folds(folds: np.ndarray, L: int, n_out_rows: int, n_mel_rows: int, bias_row: int,
+                   hop: int) -> None:
+    """The row checks ftmi_wavernn_packed makes on a host table (csrc/wavernn.hip check_fold),
+    for a table that goes to the device: there the library cannot read it back."""
+    f = np.asarray(folds)
+    if f.ndim != 2 or f.shape[1] != len(_lib.WR_FOLD_COLS) or f.dtype != np.int32 or f.shape[0] == 0:
+        raise ValueError(f'fold table: int32 (n, {len(_lib.WR_FOLD_COLS)}) expected, got {f.dtype} {f.shape}')
+    mel0, cond0, g0, n, pb, orow = (f[:, i].astype(np.int64) for i in range(6))
+    ok = ((g0 >= 0) & (n > 0) & (g0 < n) & (g0 <= 2 ** 31 - 1 - L) & (orow >= 0) & (orow < n_out_rows)
+          & (pb >= 0) & (mel0 >= 0) & (mel0 + n <= n_mel_rows) & (cond0 >= 0)
+          & (cond0 + (n - 1) // hop < bias_row))
+    if not ok.all():
+        i = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f'fold descriptor {i} out of range: {dict(zip(_lib.WR_FOLD_COLS, f[i].tolist()))}')
+
+
+def wavernn_packed(args, folds: np.ndarray, launch_steps, flops: float, device, host_table=False):
+    """Enqueue ftmi_wavernn_packed (args: a filled _lib.WaveRNNPackedArgs without the table; the
+    caller keeps every buffer alive).  folds: host int32 (n, 8) table (_lib.WR_FOLD_COLS),
+    checked here and handed over as device memory (host_table: handed over as it is, for the
+    library to check and stage); launch_steps: per-launch step counts or None.  Returns the
+    table handed over (to be kept until the stream has run the call)."""
+    folds = np.ascontiguousarray(folds, dtype=np.int32)
+    if host_table:
+        tbl = folds
+        args.folds = folds.ctypes.data
+    else:
+        check_wr_folds(folds, args.L, args.n_out_rows, args.n_mel_rows, args.bias_row, args.hop)
+        tbl = torch.from_numpy(folds).to(device)
+        args.folds = tbl.data_ptr()
+    args.n_folds = folds.shape[0]
+    steps = None
+    if launch_steps is not None:
+        steps = (ctypes.c_int32 * len(launch_steps))(*[int(v) for v in launch_steps])
+        if len(launch_steps) != -(-folds.shape[0] // 32):
+            raise ValueError('launch_steps: one entry per launch of 32 folds')
+        args.launch_steps = ctypes.cast(steps, ctypes.c_void_p).value
+    args.status = status_word(device).data_ptr()
+    mode = 'forward' if args.xin else 'generate'
+    F, L = folds.shape[0], args.L
+    launch('ftmi_wavernn_packed', f'wavernn_packed[{mode},F={F},L={L},NC={args.n_classes}]', flops,
+           4.0 * F * L * (1 + (args.n_classes if args.logits else 0)), ctypes.byref(args), _stream())
+    return tbl
+
+
+def wr_unfold_packed(samples: torch.Tensor, items: np.ndarray, target: int, overlap: int,
+                     batched: bool, mu_law: bool, n_classes: int, fade_len: int) -> torch.Tensor:
+    """ftmi_wr_unfold of every utterance of a packed (F, L) sample matrix in one launch ->
+    flat float64 waves; items: host int32 (n, 4) table (_lib.WR_ITEM_COLS), checked here against
+    ftmi_wr_unfold's shape rules and handed over as device memory."""
+    _dev(samples)
+    samples = samples.contiguous()
+    F, L = samples.shape
+    it = np.ascontiguousarray(items, dtype=np.int32)
+    if it.ndim != 2 or it.shape[1] != len(_lib.WR_ITEM_COLS) or it.shape[0] == 0:
+        raise ValueError(f'item table: int32 (n, {len(_lib.WR_ITEM_COLS)}) expected, got {it.shape}')
+    r0, nf, wl, off = (it[:, i].astype(np.int64) for i in range(4))
+    out_len = int((off + wl).max())
+    ok = (r0 >= 0) & (nf > 0) & (r0 + nf <= F) & (wl > 0) & (wl >= fade_len) & (off >= 0)
+    ok &= (wl <= nf * (target + overlap) + overlap) if batched else ((nf == 1) & (wl <= L))
+    if not ok.all():
+        i = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f'item {i} out of range: {dict(zip(_lib.WR_ITEM_COLS, it[i].tolist()))}')
+    tbl = torch.from_numpy(it).to(samples.device)
+    out = torch.empty(out_len, device=samples.device, dtype=torch.float64)
+    launch('ftmi_wr_unfold_packed', f'wr_unfold_packed[F={F},L={L},items={it.shape[0]}]', 0,
+           4.0 * F * L + 8.0 * out_len, samples.data_ptr(), F, L, tbl.data_ptr(), it.shape[0], target,
+           overlap, int(batched), int(mu_law), n_classes, fade_len, out.data_ptr(), out_len, _stream())
+    return out
+
+
 # ---- Tacotron decoder loop (csrc/tacotron.hip) ---------------------------------------------
 
 TACO_MAX_TOKENS, TACO_MAX_BATCH = 512, 2  # include/ftmi.h FTMI_TACO_MAX_*

@@ -8,7 +8,9 @@ teacher-forced `forward(x, mels)`, `fold_with_overlap`, `xfade_and_unfold`, `pad
 `get_step`, `num_params`.  No torch compute layers: the upsampling network runs on the
 GEMM kernels (BatchNorm folded into the 1x1 / k5 convolutions) and `ftmi_wr_stretch_conv`,
 the sample loop on ONE persistent launch (`ftmi_wavernn`, csrc/wavernn.hip), the
-crossfade / mu-law tail on `ftmi_wr_unfold`.
+crossfade / mu-law tail on `ftmi_wr_unfold`.  Beyond the reference: `generate_batch(mels, ...)`
+vocodes a list of utterances of unequal length in shared launches (`pack_plan`,
+`generate_samples_batch`; `ftmi_wavernn_packed`, `ftmi_wr_unfold_packed`).
 
 Randomness: the reference draws with torch's global generator (Categorical / uniform_);
 here every draw comes from a counter-based Philox4x32-10 stream whose key is taken from
@@ -18,9 +20,10 @@ torch's CPU generator at each call (`torch.manual_seed` makes a run reproducible
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from pathlib import Path
-from typing import Any, Dict, Optional, Union
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -112,6 +115,45 @@ def _fold_bn(conv_w: torch.Tensor, bn: BatchNorm1dParams):
     scale, shift = bn.folded()
     w = (conv_w.detach().double() * scale.double()[:, None, None]).float()
     return w.permute(0, 2, 1).contiguous().reshape(w.size(0), -1), shift
+
+
+@dataclasses.dataclass
+class PackPlan:
+    """WaveRNN.pack_plan's result.  Table order is the order of the sample matrix's rows:
+    batched the caller's, unbatched longest first; `order[k]` is the caller's index of table
+    utterance k.
+      folds         int32 (F, 8) rows of _lib.WR_FOLD_COLS, keys still zero (table(seeds))
+      item_of_fold  (F,) table utterance of each fold
+      launches      [(NBV, NI, first_fold, n_folds)] as ftmi_wavernn_packed will launch
+      launch_steps  unbatched: each launch's step count (its longest row); batched: None (L)
+      items         int32 (n, 4) rows of _lib.WR_ITEM_COLS: fold rows, wave length, offset in
+                    the flat output of ftmi_wr_unfold_packed"""
+    batched: bool
+    target: int
+    overlap: int
+    L: int
+    hop: int
+    lengths: List[int]
+    order: List[int]
+    folds: np.ndarray
+    item_of_fold: np.ndarray
+    launches: List[Tuple[int, int, int, int]]
+    launch_steps: Optional[List[int]]
+    items: np.ndarray
+
+    def rows(self, i: int) -> slice:
+        """The sample-matrix rows of the caller's utterance i."""
+        r0, nf = self.items[self.order.index(i), :2].tolist()
+        return slice(r0, r0 + nf)
+
+    def table(self, seeds: Sequence[int]) -> np.ndarray:
+        """The fold table with each utterance's Philox key (seeds in the caller's order)."""
+        key = np.asarray([int(seeds[i]) & 0xFFFFFFFFFFFFFFFF for i in self.order], dtype=np.uint64)
+        t = self.folds.copy()
+        k = key[self.item_of_fold]
+        t[:, 6] = (k & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
+        t[:, 7] = (k >> np.uint64(32)).astype(np.uint32).view(np.int32)
+        return t
 
 
 class WaveRNN(Packed):
@@ -332,6 +374,153 @@ class WaveRNN(Packed):
                                 20 * hop)
             out = wav.cpu().numpy()
         self.train()
+        return out
+
+    # ---- many utterances of unequal length in shared launches ---------------------------------
+    def pack_plan(self, lengths: Sequence[int], batched: bool = True, target: int = 11000,
+                  overlap: int = 550) -> 'PackPlan':
+        """Host-only: the fold descriptors (include/ftmi.h ftmi_wr_fold) and the launches of
+        utterances of `lengths` mel frames vocoded together.  Batched: each utterance's folds
+        (fold_with_overlap's count) consecutively, in the order given.  Unbatched: one row per
+        utterance, longest first (a launch runs its longest row), `order` leading back."""
+        lengths = [int(t) for t in lengths]
+        if not lengths or min(lengths) < 2:
+            raise ValueError(f'pack_plan needs utterances of at least 2 mel frames, got {lengths}')
+        hop = int(np.prod(self.upsample.scales))
+        n = len(lengths)
+        order = list(range(n)) if batched else sorted(range(n), key=lambda i: -lengths[i])
+        stride = target + overlap
+        folds, items, item_of_fold = [], [], []
+        mel0 = cond0 = row = off = 0
+        for k, i in enumerate(order):
+            T = lengths[i]
+            rows = T * hop  # generate pads `pad` frames a side, the upsampling crops them again
+            nf = self._fold_shape(rows, 1, True, target, overlap)[0] if batched else 1
+            if nf <= 0:
+                raise ValueError(f'utterance {i}: {rows} samples fold into no row at target {target}, '
+                                 f'overlap {overlap}')
+            for j in range(nf):
+                folds.append((mel0, cond0, j * stride if batched else 0, rows, j, row + j, 0, 0))
+                item_of_fold.append(k)
+            wave_len = (T - 1) * self.hop_length
+            items.append((row, nf, wave_len, off))
+            mel0, cond0, row, off = mel0 + rows, cond0 + T, row + nf, off + wave_len
+        folds = np.asarray(folds, dtype=np.int32)
+        launches, steps, f0 = [], [], 0
+        while f0 < row:  # ftmi_wavernn's host loop (csrc/wavernn.hip)
+            b = min(row - f0, 32)
+            ni = 2 if b >= 2 else 1
+            bi = -(-b // ni)
+            nbv = (8 if bi <= 8 else 16) if ni == 2 else (8 if b <= 8 else 16 if b <= 16 else 32)
+            launches.append((nbv, ni, f0, b))
+            steps.append(int(folds[f0:f0 + b, 3].max()))
+            f0 += b
+        L = target + 2 * overlap if batched else int(folds[:, 3].max())
+        return PackPlan(batched=bool(batched), target=target, overlap=overlap, L=L, hop=hop,
+                        lengths=lengths, order=order, folds=folds,
+                        item_of_fold=np.asarray(item_of_fold, dtype=np.int64), launches=launches,
+                        launch_steps=None if batched else steps,
+                        items=np.asarray(items, dtype=np.int32))
+
+    def _condition_batch(self, mels, plan: 'PackPlan'):
+        """The upsampling network per utterance (table order), rows concatenated: (mel rows
+        (sum T_i hop, feat), aux frames (sum T_i, res_out))."""
+        dev = self.step.device
+        ups, frs = [], []
+        for i in plan.order:
+            m = torch.as_tensor(mels[i]).to(device=dev, dtype=_f32)
+            m = m.unsqueeze(0) if m.dim() == 2 else m
+            if m.dim() != 3 or m.size(0) != 1 or m.size(2) != plan.lengths[i]:
+                raise ValueError(f'utterance {i}: (feat, T) or (1, feat, T) with T = {plan.lengths[i]} '
+                                 f'expected, got {tuple(m.shape)}')
+            m_up, frames = self._upsample(self.pad_tensor(m.transpose(1, 2), pad=self.pad, side='both'))
+            ups.append(m_up[0])
+            frs.append(frames[0])
+        return torch.cat(ups, 0).contiguous(), torch.cat(frs, 0)
+
+    def _run_packed(self, m_rows, frames, plan: 'PackPlan', seeds, xin=None, host_table=False):
+        """ftmi_wavernn_packed over the plan's table: the (F, L) samples, or teacher-forced
+        (xin (F, L)) the (F, L, n_classes) logits.  seeds: per utterance, caller's order.
+        host_table: hand the table over as host memory (the library checks and stages it)."""
+        _, _, (waux, bias, waux3), rec = self.packed_weights()
+        dev = m_rows.device
+        rows = torch.cat([frames, torch.zeros(1, frames.size(1), device=dev, dtype=_f32)], 0)
+        cond, _ = ops.conv1d(rows.unsqueeze(0), waux, 1, 0, bias=bias, w_split=waux3)
+        a = _lib.WaveRNNPackedArgs()
+        for k, v in rec.items():
+            setattr(a, k, v.data_ptr())
+        F, L = plan.folds.shape[0], plan.L
+        a.cond, a.mel = cond.data_ptr(), m_rows.data_ptr()
+        a.bias_row, a.n_mel_rows, a.n_out_rows = frames.size(0), m_rows.size(0), F
+        a.hop, a.L, a.n_classes, a.mol = plan.hop, L, self.n_classes, int(self.mode == 'MOL')
+        a.rnn_dims, a.fc_dims, a.feat_dims, a.aux_dims = self.rnn_dims, self.fc_dims, self.feat_dims, self.aux_dims
+        ws = ops.wavernn_workspace(dev)
+        a.workspace = ws.data_ptr()
+        self.__dict__['_ftmi_last_ws'] = ws
+        if xin is not None:
+            xin = xin.to(device=dev, dtype=_f32).contiguous()
+            if tuple(xin.shape) != (F, L):
+                raise ValueError(f'xin {tuple(xin.shape)}: one row of {L} samples per fold ({F}) expected')
+            a.xin = xin.data_ptr()
+            # rows shorter than L (unbatched) are written up to their launch's steps only
+            out = torch.zeros(F, L, self.n_classes, device=dev, dtype=_f32)
+            a.logits = out.data_ptr()
+        else:
+            out = torch.zeros(F, L, device=dev, dtype=_f32)
+            a.samples = out.data_ptr()
+        R, Fd = self.rnn_dims, self.fc_dims
+        per_step = 2.0 * (3 * R * R * 3 + Fd * R + Fd * Fd + self.n_classes * Fd + (6 * R + Fd) * self.feat_dims)
+        tbl = ops.wavernn_packed(a, plan.table(seeds), plan.launch_steps, per_step * F * L, dev,
+                                 host_table=host_table)
+        if host_table:  # the library reads the host table in stream order
+            torch.cuda.current_stream(dev).synchronize()
+        del tbl
+        return out
+
+    def generate_samples_batch(self, mels, batched=True, target=11000, overlap=550,
+                               seeds: Optional[Sequence[int]] = None):
+        """generate_samples for a sequence of utterances ((feat, T_i) or (1, feat, T_i), any
+        device) in shared launches -> (the packed (F, L) sample matrix on the device, the
+        PackPlan that says which rows are whose).  seeds: one Philox key per utterance
+        (default: one draw from torch's CPU generator each, in the order given); utterance i
+        draws the stream generate_samples(mels[i], seed=seeds[i]) draws."""
+        mels = list(mels)
+        if seeds is None:
+            seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in mels]
+        if len(seeds) != len(mels):
+            raise ValueError(f'{len(seeds)} seeds for {len(mels)} utterances')
+        plan = self.pack_plan([torch.as_tensor(m).size(-1) for m in mels], batched, target, overlap)
+        dev = self.step.device
+        with torch.no_grad():
+            def run():
+                m_rows, frames = self._condition_batch(mels, plan)
+                return self._run_packed(m_rows, frames, plan, seeds)
+            return ops.run_checked(run, dev), plan
+
+    def generate_batch(self, mels, batched, target, overlap, mu_law, seeds=None,
+                       silent=False) -> List[np.ndarray]:
+        """generate for a sequence of utterances of unequal length: their folds share launches of
+        up to 32 (one launch per 32 folds instead of at least one per utterance), one tail
+        launch and one device-to-host copy serve them all.  Returns each utterance's float64
+        wave of (T_i - 1) hop samples, in the order given."""
+        self.eval()
+        mu_law = mu_law if self.mode == 'RAW' else False
+        hop = self.hop_length
+        mels = list(mels)
+        for m in mels:
+            T = torch.as_tensor(m).size(-1)
+            if (T - 1) * hop < 20 * hop:
+                raise ValueError(f'{T} mel frames: the 20-hop fade-out of the reference (:259-261) '
+                                 f'needs at least 21')
+        smp, plan = self.generate_samples_batch(mels, batched, target, overlap, seeds)
+        with torch.no_grad():
+            wav = ops.wr_unfold_packed(smp, plan.items, target, overlap, batched, mu_law,
+                                       self.n_classes, 20 * hop).cpu().numpy()
+        self.train()
+        out: List[Optional[np.ndarray]] = [None] * len(mels)
+        for k, i in enumerate(plan.order):
+            _, _, n, off = plan.items[k].tolist()
+            out[i] = wav[off:off + n].copy()
         return out
 
     # ---- the reference's helpers ------------------------------------------------------------

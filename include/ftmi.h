@@ -846,6 +846,68 @@ int ftmi_wr_unfold(const float *samples, int32_t B, int32_t L, int32_t target, i
                    int32_t batched, int32_t mu_law, int32_t n_classes, int32_t wave_len,
                    int32_t fade_len, double *out, ftmi_stream_t stream);
 
+/* Packed sample loop: the folds of MANY utterances of unequal length share launches.  Each
+ * fold is one row of a descriptor table in place of (fold0 + b, fold_stride, item_rows):
+ *   mel_row0   first row of its utterance in `mel` (the utterances' upsampled rows, concatenated)
+ *   cond_row0  first row of its utterance's frames in `cond`
+ *   g0         the fold's start inside the utterance (batched: fold index * fold_stride; else 0)
+ *   n_rows     the utterance's upsampled length; position g = g0 + t >= n_rows is padding
+ *              (zero mel row, cond row bias_row), exactly like ftmi_wavernn's fold padding
+ *   philox_b   word b of the Philox counters (t, b, k/4, .): the fold's index within ITS OWN
+ *              utterance, so an utterance draws the stream it draws when run alone
+ *   out_row    its row of xin / samples / logits (L floats, L * n_classes for logits)
+ *   k0, k1     the utterance's Philox key (seed & 0xffffffff, seed >> 32)
+ * 32 bytes a row; the table is 16-B aligned. */
+typedef struct {
+  int32_t mel_row0, cond_row0, g0, n_rows, philox_b, out_row;
+  uint32_t k0, k1;
+} ftmi_wr_fold;
+
+/* Arguments of ftmi_wavernn_packed: the weights, cond, mel, xin / samples / logits, workspace
+ * and status of ftmi_wavernn_args, and
+ *   folds         n_folds descriptors.  Device memory: used as it is, its rows checked by
+ *                 whoever filled it.  Host memory: every row is checked here (FTMI_E_SHAPE for
+ *                 g0 < 0, g0 >= n_rows, n_rows <= 0, out_row outside [0, n_out_rows), rows
+ *                 past n_mel_rows / bias_row) and the table is copied in stream order; it
+ *                 must stay unchanged until the stream has passed the call.
+ *   launch_steps  host array, one entry per launch (ceil(n_folds / 32)), 1 .. L: the steps
+ *                 that launch runs (rows of unequal length: its longest row); NULL: L each.
+ *   L             row stride of xin / samples / logits and the default step count
+ *   n_out_rows, n_mel_rows, bias_row   rows of samples, of mel, and cond's last row. */
+typedef struct {
+  const float *w_hh1, *w_hh2, *w_ih2a, *w_fc1a, *w_fc2a, *w_fc3, *b_fc3, *b_hh1, *b_hh2;
+  const float *u1, *u2, *v1, *wm, *cond, *mel;
+  const float *xin;
+  float *samples, *logits;
+  void *workspace;
+  uint32_t *status;
+  const ftmi_wr_fold *folds;
+  const int32_t *launch_steps;
+  int32_t n_folds, L, n_out_rows, n_mel_rows, bias_row, hop, n_classes, mol;
+  int32_t rnn_dims, fc_dims, feat_dims, aux_dims;
+} ftmi_wavernn_packed_args;
+
+/* ftmi_wavernn's launches (<= 32 folds each in table order, two instances from two folds on,
+ * the same kernels and hand-off protocol) over a descriptor table.  Nothing is launched
+ * when an argument or a host table row is refused. */
+int ftmi_wavernn_packed(const ftmi_wavernn_packed_args *args, ftmi_stream_t stream);
+
+/* One utterance of a packed sample matrix: its fold rows [first_row, first_row + n_folds),
+ * its wave of wave_len float64 samples at out + out_offset. */
+typedef struct {
+  int32_t first_row, n_folds, wave_len, out_offset;
+} ftmi_wr_item;
+
+/* ftmi_wr_unfold for every utterance of a packed (n_rows, L) sample matrix in one launch;
+ * each utterance's slice is bit-equal to ftmi_wr_unfold on its rows.  items: n_items rows,
+ * 16-B aligned, device or host memory under the rule of ftmi_wavernn_packed_args.folds
+ * (host rows are held to ftmi_wr_unfold's shape rules and to out_len: FTMI_E_SHAPE).
+ * Unbatched: n_folds = 1.  out_len <= 2^30, n_items <= 65535 (else FTMI_E_UNSUPPORTED). */
+int ftmi_wr_unfold_packed(const float *samples, int32_t n_rows, int32_t L, const ftmi_wr_item *items,
+                          int32_t n_items, int32_t target, int32_t overlap, int32_t batched,
+                          int32_t mu_law, int32_t n_classes, int32_t fade_len, double *out,
+                          int64_t out_len, ftmi_stream_t stream);
+
 /* ---- Tacotron decoder loop (models/tacotron.py; gen_tacotron.py, train_tacotron.py's
  * attention pass) ---------------------------------------------------------------------------
  * Fixed architecture of the reference config (config.yaml:51-61): decoder_dims = 256 (the
