@@ -21,9 +21,10 @@ _lib = None
 
 c_int, c_int64, c_float, c_void_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 P = c_void_p  # every device pointer travels as void*
-# 22 still: ftmi_wavernn_packed and ftmi_wr_unfold_packed are new symbols; no existing signature
-# or struct changed, so a caller built against the earlier 22 keeps working (the version is
-# bumped on a signature change, include/ftmi.h)
+# 22 still: ftmi_wavernn_packed, ftmi_wr_unfold_packed and the host-only queries
+# ftmi_wavernn_route, ftmi_wr_check_folds, ftmi_wr_check_items are new symbols; no existing
+# signature or struct changed, so a caller built against the earlier 22 keeps working (the
+# version is bumped on a signature change, include/ftmi.h)
 ABI_VERSION = 22
 MMA_F32, MMA_BF16X6, MMA_F16X3 = 0, 1, 2
 
@@ -219,6 +220,10 @@ SIGNATURES = {
     'ftmi_wavernn_packed': (c_int, [ctypes.POINTER(WaveRNNPackedArgs), P]),
     'ftmi_wr_unfold_packed': (c_int, [P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, P, c_int64, P]),
+    'ftmi_wavernn_route': (c_int, [c_int, P, c_int, ctypes.POINTER(c_int)]),
+    'ftmi_wr_check_folds': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    'ftmi_wr_check_items': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64,
+                                    ctypes.POINTER(c_int)]),
     'ftmi_tacotron_decoder_workspace_bytes': (c_int64, [c_int, c_int]),
     'ftmi_tacotron_decoder': (c_int, [ctypes.POINTER(TacoArgs), P]),
     'ftmi_align_workspace_bytes': (c_int64, [c_int, c_int, c_int]),

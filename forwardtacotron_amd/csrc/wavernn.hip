@@ -1044,27 +1044,41 @@ int cu_count() {
   return cus;
 }
 
-}  // namespace
-
-constexpr int WR_NI_MAX = 2;  // instances per launch
-
-extern "C" int64_t ftmi_wavernn_workspace_bytes(void) {
-  return (int64_t)(WS_CTRL + WR_NI_MAX * (4 * XS_VEC + XS_Z)) * 4;
+// The two debug switches, read once per call.  FTMI_WR_NI=1: one instance per launch (A/B
+// runs); FTMI_WR_STAMPS=1: per-phase s_memtime sums of WG 0 / WG 128.
+struct WrSwitches {
+  int ni, stamps;
+};
+WrSwitches wr_switches() {
+  const char *ni = getenv("FTMI_WR_NI"), *st = getenv("FTMI_WR_STAMPS");
+  return {ni ? atoi(ni) : 2, st ? atoi(st) : 0};
 }
 
-extern "C" uint32_t ftmi_set_wavernn_spin_limit(uint32_t limit) {
-  const uint32_t old = g_wr_spin;
-  g_wr_spin = limit ? limit : SPIN_DEFAULT;
-  return old;
+// The one statement of the launch rule: visit(launch, its index) for each launch of n_folds
+// folds, until one returns a status.  <= WR_NBMAX folds per launch in fold order; two
+// instances (each the whole pipeline on 128 workgroups, half the folds) from two folds on:
+// the per-step hand-off latency is paid once for both (c2-size mel, 19 folds: 23.95 against
+// 31.8 us/step with one); NBV: the least of 8 / 16 / 32 that holds an instance's folds.
+template <class F>
+int wr_route(int n_folds, const WrSwitches &sw, F &&visit) {
+  ftmi_wr_launch l = {};
+  for (int li = 0; l.fold0 < n_folds; l.fold0 += l.n_folds, ++li) {
+    l.n_folds = n_folds - l.fold0 < WR_NBMAX ? n_folds - l.fold0 : WR_NBMAX;
+    l.ni = (l.n_folds >= 2 && sw.ni != 1) ? 2 : 1;
+    const int bi = (l.n_folds + l.ni - 1) / l.ni;
+    l.nbv = bi <= 8 ? 8 : bi <= 16 ? 16 : 32;
+    if (int rc = visit(l, li)) return rc;
+  }
+  return FTMI_OK;
 }
 
-extern "C" int ftmi_wavernn(const ftmi_wavernn_args *a, ftmi_stream_t stream) {
-  if (!a) return FTMI_E_ARG;
+// What ftmi_wavernn_args and ftmi_wavernn_packed_args share (same field names), in the order
+// both entry points check it.  counts_ok: the entry point's own counts.
+template <class A>
+int wr_check_model(const A *a, bool counts_ok) {
   if (!a->w_hh1 || !a->w_hh2 || !a->w_ih2a || !a->w_fc1a || !a->w_fc2a || !a->w_fc3 ||
       !a->b_fc3 || !a->b_hh1 || !a->b_hh2 || !a->u1 || !a->u2 || !a->v1 || !a->wm || !a->cond ||
-      !a->mel || !a->workspace)
-    return FTMI_E_ARG;
-  if (a->B <= 0 || a->L <= 0 || a->hop <= 0 || a->item_rows <= 0 || a->frames_per_item <= 0)
+      !a->mel || !a->workspace || !counts_ok || a->L <= 0 || a->hop <= 0)
     return FTMI_E_ARG;
   if (a->rnn_dims != WR_R || a->fc_dims != WR_F || a->feat_dims != WR_NM || a->aux_dims != WR_NA)
     return FTMI_E_UNSUPPORTED;
@@ -1072,69 +1086,40 @@ extern "C" int ftmi_wavernn(const ftmi_wavernn_args *a, ftmi_stream_t stream) {
   if (a->mol ? a->n_classes != 30
              : (a->n_classes < 2 || a->n_classes > WR_F || (a->n_classes & (a->n_classes - 1)) != 0))
     return FTMI_E_UNSUPPORTED;
-  if (a->xin ? !a->logits : !a->samples) return FTMI_E_ARG;
-  if (a->batched && a->fold_stride <= 0) return FTMI_E_ARG;
-  if (!ftmi_aligned16(a->mel) || !ftmi_aligned16(a->workspace)) return FTMI_E_ALIGN;
-  if (cu_count() < WR_GRID) return FTMI_E_UNSUPPORTED;
-  hipStream_t s = ftmi_hs(stream);
-  WrParams p{};
+  return (a->xin ? !a->logits : !a->samples) ? FTMI_E_ARG : FTMI_OK;
+}
+
+template <auto K, class P>
+int wr_go(const P &p, int ni, hipStream_t s) {
+  if (int rc = ftmi_resident_ok((const void *)K, WR_GRID, WR_NT * ni, 0)) return rc;
+  hipLaunchKernelGGL(K, dim3(WR_GRID), dim3(WR_NT * ni), 0, s, p);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
+}
+
+// The fields both argument structs fill, then every launch of wr_route over n_folds folds on
+// its <NBV, NI, PK> instantiation.  steps: per-launch step counts (NULL: a->L each).
+template <bool PK, class P, class A>
+int wr_run(P &p, const A *a, int n_folds, const int32_t *steps, const WrSwitches &sw, hipStream_t s) {
   p.w_hh1 = a->w_hh1, p.w_hh2 = a->w_hh2, p.w_ih2a = a->w_ih2a;
   p.w_fc1a = a->w_fc1a, p.w_fc2a = a->w_fc2a, p.w_fc3 = a->w_fc3, p.b_fc3 = a->b_fc3;
   p.b_hh1 = a->b_hh1, p.b_hh2 = a->b_hh2, p.u1 = a->u1, p.u2 = a->u2, p.v1 = a->v1;
   p.wm = a->wm, p.cond = a->cond, p.mel = a->mel;
-  p.bias_row = a->bias_row, p.item_rows = a->item_rows, p.frames_per_item = a->frames_per_item;
-  p.hop = a->hop, p.fold_stride = a->fold_stride, p.batched = a->batched;
+  p.bias_row = a->bias_row, p.hop = a->hop;
   p.xin = a->xin, p.samples = a->samples, p.logits = a->logits;
-  unsigned *ws = (unsigned *)a->workspace;
-  p.ws = ws;
-  p.xch = (float *)(ws + WS_CTRL);
-  p.status = a->status;
-  p.L = a->L, p.NC = a->n_classes, p.mol = a->mol;
-  p.k0 = (unsigned)(a->seed & 0xFFFFFFFFull), p.k1 = (unsigned)(a->seed >> 32);
-  p.spin_limit = g_wr_spin;
-  static const int stamps_env = [] {
-    const char *v = getenv("FTMI_WR_STAMPS");
-    return v ? atoi(v) : 0;
-  }();
-  p.stamps = stamps_env;
-  // two instances (each the whole pipeline on 128 workgroups, half the folds) whenever
-  // there are two folds to share: the per-step hand-off latency is paid once for both
-  const int per_launch = WR_NBMAX;  // NI = 2: 2 x 16 (the LDS holds the GRU weights)
-  for (int f0 = 0; f0 < a->B; f0 += p.B) {
-    p.fold0 = f0;
-    p.B = a->B - f0 < per_launch ? a->B - f0 : per_launch;
-    // two instances from two folds on (c2-size mel, 19 folds: 23.95 against 31.8 us/step
-    // with one); FTMI_WR_NI=1 forces one instance (A/B runs)
-    static const int ni_env = [] {
-      const char *v = getenv("FTMI_WR_NI");
-      return v ? atoi(v) : 2;
-    }();
-    const int ni = (p.B >= 2 && ni_env != 1) ? 2 : 1;
-    const int bi = (p.B + ni - 1) / ni;
+  p.ws = (unsigned *)a->workspace, p.xch = (float *)(p.ws + WS_CTRL), p.status = a->status;
+  p.NC = a->n_classes, p.mol = a->mol, p.spin_limit = g_wr_spin, p.stamps = sw.stamps;
+  return wr_route(n_folds, sw, [&](const ftmi_wr_launch &l, int li) -> int {
+    p.fold0 = l.fold0, p.B = l.n_folds, p.L = steps ? steps[li] : a->L;
     hipError_t e = hipMemsetAsync(a->workspace, 0, (size_t)ftmi_wavernn_workspace_bytes(), s);
     if (e != hipSuccess) return (int)e;
-#define FTMI_WR_LAUNCH(NBV_, NI_)                                                            \
-  do {                                                                                       \
-    if (int rc = ftmi_resident_ok((const void *)wavernn_kernel<NBV_, NI_>, WR_GRID, WR_NT * NI_, 0)) \
-      return rc;                                                                             \
-    hipLaunchKernelGGL((wavernn_kernel<NBV_, NI_>), dim3(WR_GRID), dim3(WR_NT * NI_), 0, s, p); \
-  } while (0)
-    if (ni == 1) {
-      p.B = p.B < WR_NBMAX ? p.B : WR_NBMAX;  // one instance: <= 32 folds per launch
-      if (p.B <= 8) FTMI_WR_LAUNCH(8, 1);
-      else if (p.B <= 16) FTMI_WR_LAUNCH(16, 1);
-      else FTMI_WR_LAUNCH(32, 1);
-    } else {
-      if (bi <= 8) FTMI_WR_LAUNCH(8, 2);
-      else FTMI_WR_LAUNCH(16, 2);
-    }
-#undef FTMI_WR_LAUNCH
-    FTMI_CHECK_LAUNCH();
-  }
-  return FTMI_OK;
+    if (l.ni == 1)
+      return l.nbv == 8    ? wr_go<wavernn_kernel<8, 1, PK>>(p, 1, s)
+             : l.nbv == 16 ? wr_go<wavernn_kernel<16, 1, PK>>(p, 1, s)
+                           : wr_go<wavernn_kernel<32, 1, PK>>(p, 1, s);
+    return l.nbv == 8 ? wr_go<wavernn_kernel<8, 2, PK>>(p, 2, s) : wr_go<wavernn_kernel<16, 2, PK>>(p, 2, s);
+  });
 }
-
-namespace {
 
 // A descriptor table handed to a packed entry point.  Device memory is used as it is (its
 // rows were checked by whoever filled it: the binding); anything else is host memory, which
@@ -1166,98 +1151,114 @@ struct StagedTable {
   }
 };
 
-int check_fold(const ftmi_wr_fold &f, const ftmi_wavernn_packed_args *a) {
-  if (f.g0 < 0 || f.n_rows <= 0 || f.g0 >= f.n_rows || f.g0 > INT32_MAX - a->L) return FTMI_E_SHAPE;
-  if (f.out_row < 0 || f.out_row >= a->n_out_rows || f.philox_b < 0) return FTMI_E_SHAPE;
-  if (f.mel_row0 < 0 || (int64_t)f.mel_row0 + f.n_rows > a->n_mel_rows) return FTMI_E_SHAPE;
+// the rule of one fold row (L steps, hop samples per cond frame)
+int check_fold(const ftmi_wr_fold &f, int L, int n_out_rows, int n_mel_rows, int bias_row, int hop) {
+  if (f.g0 < 0 || f.n_rows <= 0 || f.g0 >= f.n_rows || f.g0 > INT32_MAX - L) return FTMI_E_SHAPE;
+  if (f.out_row < 0 || f.out_row >= n_out_rows || f.philox_b < 0) return FTMI_E_SHAPE;
+  if (f.mel_row0 < 0 || (int64_t)f.mel_row0 + f.n_rows > n_mel_rows) return FTMI_E_SHAPE;
   // the last frame a real position reads is below the bias row
-  if (f.cond_row0 < 0 || (int64_t)f.cond_row0 + (f.n_rows - 1) / a->hop >= a->bias_row) return FTMI_E_SHAPE;
+  if (f.cond_row0 < 0 || (int64_t)f.cond_row0 + (f.n_rows - 1) / hop >= bias_row) return FTMI_E_SHAPE;
+  return FTMI_OK;
+}
+
+// the rule of one utterance of an (n_rows, L) sample matrix unfolded into out_len samples:
+// the only statement of the unfold shape rules (ftmi_wr_unfold: one item from row 0)
+int check_item(const ftmi_wr_item &it, int n_rows, int L, int target, int overlap, int batched,
+               int fade_len, int64_t out_len) {
+  if (it.first_row < 0 || it.n_folds <= 0 || (int64_t)it.first_row + it.n_folds > n_rows) return FTMI_E_SHAPE;
+  if (it.wave_len <= 0 || it.wave_len < fade_len) return FTMI_E_SHAPE;  // the reference's fade-out needs 20 hops
+  if (batched ? (int64_t)it.wave_len > (int64_t)it.n_folds * (target + overlap) + overlap
+              : (it.n_folds != 1 || it.wave_len > L))
+    return FTMI_E_SHAPE;
+  if (it.out_offset < 0 || (int64_t)it.out_offset + it.wave_len > out_len) return FTMI_E_SHAPE;
   return FTMI_OK;
 }
 
 }  // namespace
 
+constexpr int WR_NI_MAX = 2;  // instances per launch
+
+extern "C" int64_t ftmi_wavernn_workspace_bytes(void) {
+  return (int64_t)(WS_CTRL + WR_NI_MAX * (4 * XS_VEC + XS_Z)) * 4;
+}
+
+extern "C" uint32_t ftmi_set_wavernn_spin_limit(uint32_t limit) {
+  const uint32_t old = g_wr_spin;
+  g_wr_spin = limit ? limit : SPIN_DEFAULT;
+  return old;
+}
+
+extern "C" int ftmi_wavernn_route(int32_t n_folds, ftmi_wr_launch *launches, int32_t capacity,
+                                  int32_t *n_launches) {
+  if (n_folds <= 0 || !n_launches || capacity < 0 || (capacity > 0 && !launches)) return FTMI_E_ARG;
+  return wr_route(n_folds, wr_switches(), [&](const ftmi_wr_launch &l, int li) {
+    if (li < capacity) launches[li] = l;
+    *n_launches = li + 1;
+    return (int)FTMI_OK;
+  });
+}
+
+extern "C" int ftmi_wavernn(const ftmi_wavernn_args *a, ftmi_stream_t stream) {
+  if (!a) return FTMI_E_ARG;
+  if (int rc = wr_check_model(a, a->B > 0 && a->item_rows > 0 && a->frames_per_item > 0)) return rc;
+  if (a->batched && a->fold_stride <= 0) return FTMI_E_ARG;
+  if (!ftmi_aligned16(a->mel) || !ftmi_aligned16(a->workspace)) return FTMI_E_ALIGN;
+  if (cu_count() < WR_GRID) return FTMI_E_UNSUPPORTED;
+  WrParams p{};
+  p.item_rows = a->item_rows, p.frames_per_item = a->frames_per_item;
+  p.fold_stride = a->fold_stride, p.batched = a->batched;
+  p.k0 = (unsigned)(a->seed & 0xFFFFFFFFull), p.k1 = (unsigned)(a->seed >> 32);
+  return wr_run<false>(p, a, a->B, nullptr, wr_switches(), ftmi_hs(stream));
+}
+
+// the first row of a host table its rule refuses: the status, the index in *bad_row
+extern "C" int ftmi_wr_check_folds(const ftmi_wr_fold *folds, int32_t n_folds, int32_t L,
+                                   int32_t n_out_rows, int32_t n_mel_rows, int32_t bias_row,
+                                   int32_t hop, int32_t *bad_row) {
+  if (!folds || n_folds <= 0 || hop <= 0) return FTMI_E_ARG;
+  for (int i = 0; i < n_folds; ++i)
+    if (int rc = check_fold(folds[i], L, n_out_rows, n_mel_rows, bias_row, hop))
+      return bad_row ? (*bad_row = i, rc) : rc;
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_wr_check_items(const ftmi_wr_item *items, int32_t n_items, int32_t n_rows,
+                                   int32_t L, int32_t target, int32_t overlap, int32_t batched,
+                                   int32_t fade_len, int64_t out_len, int32_t *bad_row) {
+  if (!items || n_items <= 0) return FTMI_E_ARG;
+  for (int i = 0; i < n_items; ++i)
+    if (int rc = check_item(items[i], n_rows, L, target, overlap, batched, fade_len, out_len))
+      return bad_row ? (*bad_row = i, rc) : rc;
+  return FTMI_OK;
+}
+
 extern "C" int ftmi_wavernn_packed(const ftmi_wavernn_packed_args *a, ftmi_stream_t stream) {
   if (!a) return FTMI_E_ARG;
-  if (!a->w_hh1 || !a->w_hh2 || !a->w_ih2a || !a->w_fc1a || !a->w_fc2a || !a->w_fc3 ||
-      !a->b_fc3 || !a->b_hh1 || !a->b_hh2 || !a->u1 || !a->u2 || !a->v1 || !a->wm || !a->cond ||
-      !a->mel || !a->workspace || !a->folds)
-    return FTMI_E_ARG;
-  if (a->n_folds <= 0 || a->L <= 0 || a->hop <= 0 || a->n_out_rows <= 0 || a->n_mel_rows <= 0 ||
-      a->bias_row <= 0)
-    return FTMI_E_ARG;
-  if (a->rnn_dims != WR_R || a->fc_dims != WR_F || a->feat_dims != WR_NM || a->aux_dims != WR_NA)
-    return FTMI_E_UNSUPPORTED;
-  if (a->mol ? a->n_classes != 30
-             : (a->n_classes < 2 || a->n_classes > WR_F || (a->n_classes & (a->n_classes - 1)) != 0))
-    return FTMI_E_UNSUPPORTED;
-  if (a->xin ? !a->logits : !a->samples) return FTMI_E_ARG;
+  if (int rc = wr_check_model(a, a->folds && a->n_folds > 0 && a->n_out_rows > 0 && a->n_mel_rows > 0 &&
+                                     a->bias_row > 0))
+    return rc;
   if (!ftmi_aligned16(a->mel) || !ftmi_aligned16(a->workspace) || !ftmi_aligned16(a->folds))
     return FTMI_E_ALIGN;
-  const int n_launches = (a->n_folds + WR_NBMAX - 1) / WR_NBMAX;
-  for (int i = 0; a->launch_steps && i < n_launches; ++i)
-    if (a->launch_steps[i] <= 0 || a->launch_steps[i] > a->L) return FTMI_E_SHAPE;
+  const WrSwitches sw = wr_switches();
+  if (a->launch_steps)  // one entry per launch
+    if (int rc = wr_route(a->n_folds, sw, [&](const ftmi_wr_launch &, int li) {
+          return a->launch_steps[li] <= 0 || a->launch_steps[li] > a->L ? FTMI_E_SHAPE : FTMI_OK;
+        }))
+      return rc;
   const bool on_device = table_on_device(a->folds);
   if (!on_device)
-    for (int i = 0; i < a->n_folds; ++i)
-      if (int rc = check_fold(a->folds[i], a)) return rc;
+    if (int rc = ftmi_wr_check_folds(a->folds, a->n_folds, a->L, a->n_out_rows, a->n_mel_rows,
+                                     a->bias_row, a->hop, nullptr))
+      return rc;
   if (cu_count() < WR_GRID) return FTMI_E_UNSUPPORTED;
   hipStream_t s = ftmi_hs(stream);
   StagedTable staged;
   if (!on_device)
     if (int rc = staged.stage(a->folds, (size_t)a->n_folds * sizeof(ftmi_wr_fold), s)) return rc;
   WrParamsPk p{};
-  p.w_hh1 = a->w_hh1, p.w_hh2 = a->w_hh2, p.w_ih2a = a->w_ih2a;
-  p.w_fc1a = a->w_fc1a, p.w_fc2a = a->w_fc2a, p.w_fc3 = a->w_fc3, p.b_fc3 = a->b_fc3;
-  p.b_hh1 = a->b_hh1, p.b_hh2 = a->b_hh2, p.u1 = a->u1, p.u2 = a->u2, p.v1 = a->v1;
-  p.wm = a->wm, p.cond = a->cond, p.mel = a->mel;
-  p.bias_row = a->bias_row, p.hop = a->hop;
-  p.xin = a->xin, p.samples = a->samples, p.logits = a->logits;
-  unsigned *ws = (unsigned *)a->workspace;
-  p.ws = ws;
-  p.xch = (float *)(ws + WS_CTRL);
-  p.status = a->status;
-  p.NC = a->n_classes, p.mol = a->mol;
-  p.spin_limit = g_wr_spin;
   p.folds = on_device ? a->folds : (const ftmi_wr_fold *)staged.dev;
   p.ldo = a->L;
-  static const int stamps_env = [] {
-    const char *v = getenv("FTMI_WR_STAMPS");
-    return v ? atoi(v) : 0;
-  }();
-  p.stamps = stamps_env;
-  static const int ni_env = [] {  // FTMI_WR_NI=1 forces one instance, as in ftmi_wavernn
-    const char *v = getenv("FTMI_WR_NI");
-    return v ? atoi(v) : 2;
-  }();
-  // ftmi_wavernn's host loop over the table: <= WR_NBMAX folds per launch in table order, two
-  // instances from two folds on, the same NBV choice, the residency check before each launch
-  for (int f0 = 0, li = 0; f0 < a->n_folds; f0 += p.B, ++li) {
-    p.fold0 = f0;
-    p.B = a->n_folds - f0 < WR_NBMAX ? a->n_folds - f0 : WR_NBMAX;
-    p.L = a->launch_steps ? a->launch_steps[li] : a->L;
-    const int ni = (p.B >= 2 && ni_env != 1) ? 2 : 1;
-    const int bi = (p.B + ni - 1) / ni;
-    hipError_t e = hipMemsetAsync(a->workspace, 0, (size_t)ftmi_wavernn_workspace_bytes(), s);
-    if (e != hipSuccess) return (int)e;
-#define FTMI_WR_LAUNCH(NBV_, NI_)                                                                  \
-  do {                                                                                             \
-    if (int rc = ftmi_resident_ok((const void *)wavernn_kernel<NBV_, NI_, true>, WR_GRID, WR_NT * NI_, 0)) \
-      return rc;                                                                                   \
-    hipLaunchKernelGGL((wavernn_kernel<NBV_, NI_, true>), dim3(WR_GRID), dim3(WR_NT * NI_), 0, s, p); \
-  } while (0)
-    if (ni == 1) {
-      if (p.B <= 8) FTMI_WR_LAUNCH(8, 1);
-      else if (p.B <= 16) FTMI_WR_LAUNCH(16, 1);
-      else FTMI_WR_LAUNCH(32, 1);
-    } else {
-      if (bi <= 8) FTMI_WR_LAUNCH(8, 2);
-      else FTMI_WR_LAUNCH(16, 2);
-    }
-#undef FTMI_WR_LAUNCH
-    FTMI_CHECK_LAUNCH();
-  }
-  return FTMI_OK;
+  return wr_run<true>(p, a, a->n_folds, a->launch_steps, sw, s);
 }
 
 extern "C" int ftmi_wr_stretch_conv(const float *x, int64_t x_batch_stride, int32_t B, int32_t W,
@@ -1283,9 +1284,8 @@ extern "C" int ftmi_wr_unfold(const float *samples, int32_t B, int32_t L, int32_
   if (B <= 0 || L <= 0 || wave_len <= 0 || fade_len < 0 || n_classes < 2) return FTMI_E_ARG;
   if (mu_law && (n_classes & (n_classes - 1)) != 0) return FTMI_E_UNSUPPORTED;
   if (batched && (target < 0 || overlap < 0 || L != target + 2 * overlap)) return FTMI_E_SHAPE;
-  if (wave_len < fade_len) return FTMI_E_SHAPE;  // the reference's fade-out needs 20 hops
-  if (batched ? (int64_t)wave_len > (int64_t)B * (target + overlap) + overlap : wave_len > L)
-    return FTMI_E_SHAPE;
+  const ftmi_wr_item all = {0, batched ? B : 1, wave_len, 0};  // unbatched: fold 0 alone, whatever B
+  if (int rc = check_item(all, B, L, target, overlap, batched, fade_len, wave_len)) return rc;
   hipLaunchKernelGGL(wr_unfold_kernel, dim3((wave_len + 255) / 256), dim3(256), 0, ftmi_hs(stream),
                      samples, B, L, target, overlap, batched, mu_law, n_classes, wave_len, fade_len, out);
   FTMI_CHECK_LAUNCH();
@@ -1305,15 +1305,10 @@ extern "C" int ftmi_wr_unfold_packed(const float *samples, int32_t n_rows, int32
   if (n_items > 65535 || out_len > ((int64_t)1 << 30)) return FTMI_E_UNSUPPORTED;  // grid y; int32 offsets
   if (!ftmi_aligned16(items)) return FTMI_E_ALIGN;
   const bool on_device = table_on_device(items);
-  for (int i = 0; !on_device && i < n_items; ++i) {  // ftmi_wr_unfold's rules, per item
-    const ftmi_wr_item &it = items[i];
-    if (it.first_row < 0 || it.n_folds <= 0 || (int64_t)it.first_row + it.n_folds > n_rows) return FTMI_E_SHAPE;
-    if (it.wave_len <= 0 || it.wave_len < fade_len) return FTMI_E_SHAPE;
-    if (batched ? (int64_t)it.wave_len > (int64_t)it.n_folds * (target + overlap) + overlap
-                : (it.n_folds != 1 || it.wave_len > L))
-      return FTMI_E_SHAPE;
-    if (it.out_offset < 0 || (int64_t)it.out_offset + it.wave_len > out_len) return FTMI_E_SHAPE;
-  }
+  if (!on_device)
+    if (int rc = ftmi_wr_check_items(items, n_items, n_rows, L, target, overlap, batched, fade_len,
+                                     out_len, nullptr))
+      return rc;
   hipStream_t s = ftmi_hs(stream);
   StagedTable staged;
   if (!on_device)

@@ -984,13 +984,22 @@ def wr_stretch_conv(x: torch.Tensor, scale: int, w: torch.Tensor, W_out: Optiona
     return y
 
 
-def wavernn(args, B: int, L: int, flops: float, device) -> None:
+def wavernn(args, B: int, L: int, flops: float, device, entry='wavernn', rows='B') -> None:
     """Enqueue ftmi_wavernn (args: a filled _lib.WaveRNNArgs; the caller keeps every buffer
-    alive).  The status word pointer is set here."""
+    alive) — or ftmi_<entry>, whose probe label calls the B rows `rows`.  The status word
+    pointer is set here."""
     args.status = status_word(device).data_ptr()
     mode = 'forward' if args.xin else 'generate'
-    launch('ftmi_wavernn', f'wavernn[{mode},B={B},L={L},NC={args.n_classes}]', flops,
+    launch(f'ftmi_{entry}', f'{entry}[{mode},{rows}={B},L={L},NC={args.n_classes}]', flops,
            4.0 * B * L * (1 + (args.n_classes if args.logits else 0)), ctypes.byref(args), _stream())
+
+
+def wavernn_route(n_folds: int):
+    """[(NBV, NI, first fold, folds)]: the launches ftmi_wavernn / ftmi_wavernn_packed issue for
+    n_folds folds under the current environment, as the library decides them."""
+    n, buf = ctypes.c_int32(0), (ctypes.c_int32 * (4 * max(n_folds, 0)))()  # room: a fold per launch
+    _lib.call('ftmi_wavernn_route', n_folds, buf, n_folds, ctypes.byref(n))
+    return [tuple(buf[4 * i:4 * i + 4]) for i in range(n.value)]
 
 
 def wavernn_workspace(device) -> torch.Tensor:
@@ -1012,20 +1021,27 @@ def wr_unfold(samples: torch.Tensor, target: int, overlap: int, batched: bool, m
     return out
 
 
+def _check_wr_table(query: str, what: str, cols, tbl: np.ndarray, *args) -> None:
+    """The library's row check of a host table (ftmi_wr_check_folds / ftmi_wr_check_items), for a
+    table that goes to the device: there the library cannot read it back."""
+    tbl, bad = np.ascontiguousarray(tbl), ctypes.c_int32(-1)
+    try:
+        _lib.call(query, tbl.ctypes.data, tbl.shape[0], *args, ctypes.byref(bad))
+    except _lib.FtmiError:
+        if bad.value < 0:  # not a row: the call's own arguments
+            raise
+        raise ValueError(f'{what} {bad.value} out of range: '
+                         f'{dict(zip(cols, tbl[bad.value].tolist()))}') from None
+
+
 def check_wr_folds(folds: np.ndarray, L: int, n_out_rows: int, n_mel_rows: int, bias_row: int,
                    hop: int) -> None:
-    """The row checks ftmi_wavernn_packed makes on a host table (csrc/wavernn.hip check_fold),
-    for a table that goes to the device: there the library cannot read it back."""
+    """The row checks ftmi_wavernn_packed makes on a host table (csrc/wavernn.hip check_fold)."""
     f = np.asarray(folds)
     if f.ndim != 2 or f.shape[1] != len(_lib.WR_FOLD_COLS) or f.dtype != np.int32 or f.shape[0] == 0:
         raise ValueError(f'fold table: int32 (n, {len(_lib.WR_FOLD_COLS)}) expected, got {f.dtype} {f.shape}')
-    mel0, cond0, g0, n, pb, orow = (f[:, i].astype(np.int64) for i in range(6))
-    ok = ((g0 >= 0) & (n > 0) & (g0 < n) & (g0 <= 2 ** 31 - 1 - L) & (orow >= 0) & (orow < n_out_rows)
-          & (pb >= 0) & (mel0 >= 0) & (mel0 + n <= n_mel_rows) & (cond0 >= 0)
-          & (cond0 + (n - 1) // hop < bias_row))
-    if not ok.all():
-        i = int(np.flatnonzero(~ok)[0])
-        raise ValueError(f'fold descriptor {i} out of range: {dict(zip(_lib.WR_FOLD_COLS, f[i].tolist()))}')
+    _check_wr_table('ftmi_wr_check_folds', 'fold descriptor', _lib.WR_FOLD_COLS, f, L, n_out_rows,
+                    n_mel_rows, bias_row, hop)
 
 
 def wavernn_packed(args, folds: np.ndarray, launch_steps, flops: float, device, host_table=False):
@@ -1043,38 +1059,29 @@ def wavernn_packed(args, folds: np.ndarray, launch_steps, flops: float, device, 
         tbl = torch.from_numpy(folds).to(device)
         args.folds = tbl.data_ptr()
     args.n_folds = folds.shape[0]
-    steps = None
     if launch_steps is not None:
-        steps = (ctypes.c_int32 * len(launch_steps))(*[int(v) for v in launch_steps])
-        if len(launch_steps) != -(-folds.shape[0] // 32):
-            raise ValueError('launch_steps: one entry per launch of 32 folds')
+        steps = (ctypes.c_int32 * len(launch_steps))(*[int(v) for v in launch_steps])  # alive to the end
+        if len(launch_steps) != len(wavernn_route(folds.shape[0])):
+            raise ValueError('launch_steps: one entry per launch (wavernn_route)')
         args.launch_steps = ctypes.cast(steps, ctypes.c_void_p).value
-    args.status = status_word(device).data_ptr()
-    mode = 'forward' if args.xin else 'generate'
-    F, L = folds.shape[0], args.L
-    launch('ftmi_wavernn_packed', f'wavernn_packed[{mode},F={F},L={L},NC={args.n_classes}]', flops,
-           4.0 * F * L * (1 + (args.n_classes if args.logits else 0)), ctypes.byref(args), _stream())
+    wavernn(args, folds.shape[0], args.L, flops, device, 'wavernn_packed', 'F')
     return tbl
 
 
 def wr_unfold_packed(samples: torch.Tensor, items: np.ndarray, target: int, overlap: int,
                      batched: bool, mu_law: bool, n_classes: int, fade_len: int) -> torch.Tensor:
     """ftmi_wr_unfold of every utterance of a packed (F, L) sample matrix in one launch ->
-    flat float64 waves; items: host int32 (n, 4) table (_lib.WR_ITEM_COLS), checked here against
-    ftmi_wr_unfold's shape rules and handed over as device memory."""
+    flat float64 waves; items: host int32 (n, 4) table (_lib.WR_ITEM_COLS), checked here by the
+    library's row check and handed over as device memory."""
     _dev(samples)
     samples = samples.contiguous()
     F, L = samples.shape
     it = np.ascontiguousarray(items, dtype=np.int32)
     if it.ndim != 2 or it.shape[1] != len(_lib.WR_ITEM_COLS) or it.shape[0] == 0:
         raise ValueError(f'item table: int32 (n, {len(_lib.WR_ITEM_COLS)}) expected, got {it.shape}')
-    r0, nf, wl, off = (it[:, i].astype(np.int64) for i in range(4))
-    out_len = int((off + wl).max())
-    ok = (r0 >= 0) & (nf > 0) & (r0 + nf <= F) & (wl > 0) & (wl >= fade_len) & (off >= 0)
-    ok &= (wl <= nf * (target + overlap) + overlap) if batched else ((nf == 1) & (wl <= L))
-    if not ok.all():
-        i = int(np.flatnonzero(~ok)[0])
-        raise ValueError(f'item {i} out of range: {dict(zip(_lib.WR_ITEM_COLS, it[i].tolist()))}')
+    out_len = int((it[:, 3].astype(np.int64) + it[:, 2]).max())  # the flat output ends with its last wave
+    _check_wr_table('ftmi_wr_check_items', 'item', _lib.WR_ITEM_COLS, it, F, L, target, overlap,
+                    int(batched), fade_len, out_len)
     tbl = torch.from_numpy(it).to(samples.device)
     out = torch.empty(out_len, device=samples.device, dtype=torch.float64)
     launch('ftmi_wr_unfold_packed', f'wr_unfold_packed[F={F},L={L},items={it.shape[0]}]', 0,

@@ -117,6 +117,13 @@ def _fold_bn(conv_w: torch.Tensor, bn: BatchNorm1dParams):
     return w.permute(0, 2, 1).contiguous().reshape(w.size(0), -1), shift
 
 
+def _num_folds(total_len: int, target: int, overlap: int) -> int:
+    """fold_with_overlap's fold count (:320-331): whole strides of target + overlap, and one
+    more (padded) fold when they do not end with the input."""
+    num_folds = (total_len - overlap) // (target + overlap)
+    return num_folds + (num_folds * (target + overlap) + overlap != total_len)
+
+
 @dataclasses.dataclass
 class PackPlan:
     """WaveRNN.pack_plan's result.  Table order is the order of the sample matrix's rows:
@@ -258,45 +265,64 @@ class WaveRNN(Packed):
         """The reference's `self.upsample(mels)` (:145 / :188): (B, feat, T) -> (mels (B, L,
         feat), aux (B, L, res_out)) with the aux stretch materialised (for tests)."""
         m, aux = self._upsample(mels.transpose(1, 2).contiguous())
-        hop = int(np.prod(self.upsample.scales))
-        return m, aux.repeat_interleave(hop, dim=1)
+        return m, aux.repeat_interleave(self._hop(), dim=1)
 
     # ---- the sample loop ---------------------------------------------------------------------
-    def _run(self, m_up, frames, *, batched, L, fold_stride, B, xin=None, seed=0, want_logits=False):
-        _, _, (waux, bias, waux3), rec = self.packed_weights()
-        dev = m_up.device
-        n_items, fpi = frames.size(0), frames.size(1)
-        rows = torch.cat([frames.reshape(-1, frames.size(2)),
-                          torch.zeros(1, frames.size(2), device=dev, dtype=_f32)], 0)
-        cond, _ = ops.conv1d(rows.unsqueeze(0), waux, 1, 0, bias=bias, w_split=waux3)
-        a = _lib.WaveRNNArgs()
-        for k, v in rec.items():
+    # The buffers the helpers below return (cond, ws, xin) are freed when the caller returns: the
+    # caching allocator hands their blocks to later allocations of this stream only, which run
+    # after the kernel (stream order).
+    def _cond(self, frame_rows):
+        """The per-frame conditioning rows (include/ftmi.h `cond`) of (n, res_out) aux frames,
+        the zero frame of the padded positions (biases only) appended as row n."""
+        _, _, (waux, bias, waux3), _ = self.packed_weights()
+        rows = torch.cat([frame_rows, torch.zeros(1, frame_rows.size(1), device=frame_rows.device,
+                                                  dtype=_f32)], 0)
+        return ops.conv1d(rows.unsqueeze(0), waux, 1, 0, bias=bias, w_split=waux3)[0]
+
+    def _model_args(self, a, cond, mel, L):
+        """The fields _lib.WaveRNNArgs and _lib.WaveRNNPackedArgs share (bias_row: cond's last
+        row, the zero frame); returns the workspace."""
+        for k, v in self.packed_weights()[3].items():
             setattr(a, k, v.data_ptr())
-        m_up = m_up.contiguous()
-        a.cond, a.mel = cond.data_ptr(), m_up.data_ptr()
-        a.bias_row, a.item_rows, a.frames_per_item = n_items * fpi, m_up.size(1), fpi
-        a.hop = int(np.prod(self.upsample.scales))
-        a.fold_stride, a.batched = fold_stride, int(batched)
-        a.B, a.L, a.n_classes, a.mol = B, L, self.n_classes, int(self.mode == 'MOL')
+        a.cond, a.mel, a.bias_row = cond.data_ptr(), mel.data_ptr(), cond.size(1) - 1
+        a.hop, a.L, a.n_classes, a.mol = self._hop(), L, self.n_classes, int(self.mode == 'MOL')
         a.rnn_dims, a.fc_dims, a.feat_dims, a.aux_dims = self.rnn_dims, self.fc_dims, self.feat_dims, self.aux_dims
-        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        ws = ops.wavernn_workspace(dev)
+        ws = ops.wavernn_workspace(mel.device)
         a.workspace = ws.data_ptr()
         self.__dict__['_ftmi_last_ws'] = ws  # diag readers (tools/wr_stamps.py)
-        out = None
-        if xin is not None:
-            xin = xin.to(device=dev, dtype=_f32).contiguous()
-            a.xin = xin.data_ptr()
-            out = torch.empty(B, L, self.n_classes, device=dev, dtype=_f32)
-            a.logits = out.data_ptr()
-        else:
-            out = torch.empty(B, L, device=dev, dtype=_f32)
+        return ws
+
+    def _attach_io(self, a, xin, n, L, dev, alloc):
+        """Teacher-forced (xin (n, L)): the (n, L, n_classes) logits; else the (n, L) samples.
+        Returns (the output, xin as handed over)."""
+        if xin is None:
+            out = alloc(n, L, device=dev, dtype=_f32)
             a.samples = out.data_ptr()
+            return out, None
+        xin = xin.to(device=dev, dtype=_f32).contiguous()
+        a.xin = xin.data_ptr()
+        out = alloc(n, L, self.n_classes, device=dev, dtype=_f32)
+        a.logits = out.data_ptr()
+        return out, xin
+
+    def _flops(self, n, L):
         R, F = self.rnn_dims, self.fc_dims
-        per_step = 2.0 * (3 * R * R * 3 + F * R + F * F + self.n_classes * F + (6 * R + F) * self.feat_dims)
-        # cond / ws / xin / m_up are freed on return: the caching allocator hands their blocks
-        # to later allocations of this stream only, which run after the kernel (stream order)
-        ops.wavernn(a, B, L, per_step * B * L, dev)
+        return 2.0 * (3 * R * R * 3 + F * R + F * F + self.n_classes * F + (6 * R + F) * self.feat_dims) * n * L
+
+    def _hop(self) -> int:
+        return int(np.prod(self.upsample.scales))
+
+    def _run(self, m_up, frames, *, batched, L, fold_stride, B, xin=None, seed=0, want_logits=False):
+        dev = m_up.device
+        cond = self._cond(frames.reshape(-1, frames.size(2)))
+        m_up = m_up.contiguous()
+        a = _lib.WaveRNNArgs()
+        ws = self._model_args(a, cond, m_up, L)
+        a.item_rows, a.frames_per_item = m_up.size(1), frames.size(1)
+        a.fold_stride, a.batched, a.B = fold_stride, int(batched), B
+        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        out, xin = self._attach_io(a, xin, B, L, dev, torch.empty)
+        ops.wavernn(a, B, L, self._flops(B, L), dev)
         return out
 
     def forward(self, x: torch.Tensor, mels: torch.Tensor) -> torch.Tensor:
@@ -332,10 +358,17 @@ class WaveRNN(Packed):
             return n_items, total_len
         if n_items != 1:
             raise ValueError('batched generation folds ONE utterance (:294-341)')
-        num_folds = (total_len - overlap) // (target + overlap)
-        if total_len - (num_folds * (overlap + target) + overlap) != 0:
-            num_folds += 1
-        return num_folds, target + 2 * overlap
+        return _num_folds(total_len, target, overlap), target + 2 * overlap
+
+    def _tail_args(self, mels, mu_law):
+        """generate's and generate_batch's rules of the tail: mu-law decoding in RAW mode only;
+        the 20-hop fade-out needs 21 frames of every utterance.  -> (mu_law, fade_len)."""
+        for m in mels:
+            T = torch.as_tensor(m).size(-1)
+            if T < 21:
+                raise ValueError(f'{T} mel frames: the 20-hop fade-out of the reference (:259-261) '
+                                 f'needs at least 21')
+        return (mu_law if self.mode == 'RAW' else False), 20 * self.hop_length
 
     def generate_samples(self, mels, batched=True, target=11000, overlap=550,
                          seed: Optional[int] = None) -> torch.Tensor:
@@ -361,17 +394,12 @@ class WaveRNN(Packed):
         float64 numpy wave of (T - 1) hop samples.  seed: the Philox key of the draws
         (default: drawn from torch's CPU generator)."""
         self.eval()
-        mu_law = mu_law if self.mode == 'RAW' else False
-        hop = self.hop_length
-        T = torch.as_tensor(mels).size(-1)
-        wave_len = (T - 1) * hop
-        if wave_len < 20 * hop:
-            raise ValueError(f'{T} mel frames: the 20-hop fade-out of the reference (:259-261) '
-                             f'needs at least 21')
+        mu_law, fade_len = self._tail_args([mels], mu_law)
+        wave_len = (torch.as_tensor(mels).size(-1) - 1) * self.hop_length
         smp = self.generate_samples(mels, batched, target, overlap, seed)
         with torch.no_grad():
             wav = ops.wr_unfold(smp, target, overlap, batched, mu_law, self.n_classes, wave_len,
-                                20 * hop)
+                                fade_len)
             out = wav.cpu().numpy()
         self.train()
         return out
@@ -386,7 +414,7 @@ class WaveRNN(Packed):
         lengths = [int(t) for t in lengths]
         if not lengths or min(lengths) < 2:
             raise ValueError(f'pack_plan needs utterances of at least 2 mel frames, got {lengths}')
-        hop = int(np.prod(self.upsample.scales))
+        hop = self._hop()
         n = len(lengths)
         order = list(range(n)) if batched else sorted(range(n), key=lambda i: -lengths[i])
         stride = target + overlap
@@ -395,7 +423,7 @@ class WaveRNN(Packed):
         for k, i in enumerate(order):
             T = lengths[i]
             rows = T * hop  # generate pads `pad` frames a side, the upsampling crops them again
-            nf = self._fold_shape(rows, 1, True, target, overlap)[0] if batched else 1
+            nf = _num_folds(rows, target, overlap) if batched else 1
             if nf <= 0:
                 raise ValueError(f'utterance {i}: {rows} samples fold into no row at target {target}, '
                                  f'overlap {overlap}')
@@ -406,15 +434,8 @@ class WaveRNN(Packed):
             items.append((row, nf, wave_len, off))
             mel0, cond0, row, off = mel0 + rows, cond0 + T, row + nf, off + wave_len
         folds = np.asarray(folds, dtype=np.int32)
-        launches, steps, f0 = [], [], 0
-        while f0 < row:  # ftmi_wavernn's host loop (csrc/wavernn.hip)
-            b = min(row - f0, 32)
-            ni = 2 if b >= 2 else 1
-            bi = -(-b // ni)
-            nbv = (8 if bi <= 8 else 16) if ni == 2 else (8 if b <= 8 else 16 if b <= 16 else 32)
-            launches.append((nbv, ni, f0, b))
-            steps.append(int(folds[f0:f0 + b, 3].max()))
-            f0 += b
+        launches = ops.wavernn_route(row)  # the library decides them (csrc/wavernn.hip wr_route)
+        steps = [int(folds[f0:f0 + b, 3].max()) for _, _, f0, b in launches]
         L = target + 2 * overlap if batched else int(folds[:, 3].max())
         return PackPlan(batched=bool(batched), target=target, overlap=overlap, L=L, hop=hop,
                         lengths=lengths, order=order, folds=folds,
@@ -442,35 +463,17 @@ class WaveRNN(Packed):
         """ftmi_wavernn_packed over the plan's table: the (F, L) samples, or teacher-forced
         (xin (F, L)) the (F, L, n_classes) logits.  seeds: per utterance, caller's order.
         host_table: hand the table over as host memory (the library checks and stages it)."""
-        _, _, (waux, bias, waux3), rec = self.packed_weights()
         dev = m_rows.device
-        rows = torch.cat([frames, torch.zeros(1, frames.size(1), device=dev, dtype=_f32)], 0)
-        cond, _ = ops.conv1d(rows.unsqueeze(0), waux, 1, 0, bias=bias, w_split=waux3)
-        a = _lib.WaveRNNPackedArgs()
-        for k, v in rec.items():
-            setattr(a, k, v.data_ptr())
         F, L = plan.folds.shape[0], plan.L
-        a.cond, a.mel = cond.data_ptr(), m_rows.data_ptr()
-        a.bias_row, a.n_mel_rows, a.n_out_rows = frames.size(0), m_rows.size(0), F
-        a.hop, a.L, a.n_classes, a.mol = plan.hop, L, self.n_classes, int(self.mode == 'MOL')
-        a.rnn_dims, a.fc_dims, a.feat_dims, a.aux_dims = self.rnn_dims, self.fc_dims, self.feat_dims, self.aux_dims
-        ws = ops.wavernn_workspace(dev)
-        a.workspace = ws.data_ptr()
-        self.__dict__['_ftmi_last_ws'] = ws
-        if xin is not None:
-            xin = xin.to(device=dev, dtype=_f32).contiguous()
-            if tuple(xin.shape) != (F, L):
-                raise ValueError(f'xin {tuple(xin.shape)}: one row of {L} samples per fold ({F}) expected')
-            a.xin = xin.data_ptr()
-            # rows shorter than L (unbatched) are written up to their launch's steps only
-            out = torch.zeros(F, L, self.n_classes, device=dev, dtype=_f32)
-            a.logits = out.data_ptr()
-        else:
-            out = torch.zeros(F, L, device=dev, dtype=_f32)
-            a.samples = out.data_ptr()
-        R, Fd = self.rnn_dims, self.fc_dims
-        per_step = 2.0 * (3 * R * R * 3 + Fd * R + Fd * Fd + self.n_classes * Fd + (6 * R + Fd) * self.feat_dims)
-        tbl = ops.wavernn_packed(a, plan.table(seeds), plan.launch_steps, per_step * F * L, dev,
+        if xin is not None and tuple(xin.shape) != (F, L):
+            raise ValueError(f'xin {tuple(xin.shape)}: one row of {L} samples per fold ({F}) expected')
+        cond = self._cond(frames)
+        a = _lib.WaveRNNPackedArgs()
+        ws = self._model_args(a, cond, m_rows, L)
+        a.n_mel_rows, a.n_out_rows = m_rows.size(0), F
+        # rows shorter than L (unbatched) are written up to their launch's steps only: zeros
+        out, xin = self._attach_io(a, xin, F, L, dev, torch.zeros)
+        tbl = ops.wavernn_packed(a, plan.table(seeds), plan.launch_steps, self._flops(F, L), dev,
                                  host_table=host_table)
         if host_table:  # the library reads the host table in stream order
             torch.cuda.current_stream(dev).synchronize()
@@ -504,18 +507,12 @@ class WaveRNN(Packed):
         launch and one device-to-host copy serve them all.  Returns each utterance's float64
         wave of (T_i - 1) hop samples, in the order given."""
         self.eval()
-        mu_law = mu_law if self.mode == 'RAW' else False
-        hop = self.hop_length
         mels = list(mels)
-        for m in mels:
-            T = torch.as_tensor(m).size(-1)
-            if (T - 1) * hop < 20 * hop:
-                raise ValueError(f'{T} mel frames: the 20-hop fade-out of the reference (:259-261) '
-                                 f'needs at least 21')
+        mu_law, fade_len = self._tail_args(mels, mu_law)
         smp, plan = self.generate_samples_batch(mels, batched, target, overlap, seeds)
         with torch.no_grad():
             wav = ops.wr_unfold_packed(smp, plan.items, target, overlap, batched, mu_law,
-                                       self.n_classes, 20 * hop).cpu().numpy()
+                                       self.n_classes, fade_len).cpu().numpy()
         self.train()
         out: List[Optional[np.ndarray]] = [None] * len(mels)
         for k, i in enumerate(plan.order):
@@ -538,12 +535,9 @@ class WaveRNN(Packed):
     def fold_with_overlap(self, x, target, overlap):
         """:294-341 (data movement; generate folds implicitly inside the kernel)."""
         _, total_len, features = x.size()
-        num_folds = (total_len - overlap) // (target + overlap)
-        extended_len = num_folds * (overlap + target) + overlap
-        remaining = total_len - extended_len
-        if remaining != 0:
-            num_folds += 1
-            x = self.pad_tensor(x, target + 2 * overlap - remaining, side='after')
+        num_folds = _num_folds(total_len, target, overlap)
+        if num_folds * (target + overlap) + overlap != total_len:  # the last fold is padded
+            x = self.pad_tensor(x, num_folds * (target + overlap) + 2 * overlap - total_len, side='after')
         folded = torch.zeros(num_folds, target + 2 * overlap, features, device=x.device, dtype=x.dtype)
         for i in range(num_folds):
             start = i * (target + overlap)

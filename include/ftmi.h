@@ -93,7 +93,8 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * ftmi_gemm_switches_digest; no existing signature changed;
  * 22: ftmi_rnn_route, ftmi_rnn_switches_digest; no existing signature changed;
  * added under 22 without a signature change: ftmi_frame_power, ftmi_trim_bounds, ftmi_peak_abs,
- * ftmi_prepare_audio). */
+ * ftmi_prepare_audio; ftmi_wavernn_packed, ftmi_wr_unfold_packed; ftmi_wavernn_route,
+ * ftmi_wr_check_folds, ftmi_wr_check_items). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -837,6 +838,23 @@ int64_t ftmi_wavernn_workspace_bytes(void);
 int ftmi_wavernn(const ftmi_wavernn_args *args, ftmi_stream_t stream);
 uint32_t ftmi_set_wavernn_spin_limit(uint32_t limit);
 
+/* One launch of the sample loop: wavernn_kernel<nbv, ni> (ni instances of up to nbv folds
+ * each) over folds [fold0, fold0 + n_folds). */
+typedef struct {
+  int32_t nbv, ni, fold0, n_folds;
+} ftmi_wr_launch;
+
+/* Host-only (launches nothing, makes no device call): the launches ftmi_wavernn (B = n_folds)
+ * and ftmi_wavernn_packed issue for n_folds folds, from the one function that decides them
+ * (csrc/wavernn.hip wr_route): <= 32 folds per launch in fold order, two instances from two
+ * folds on, nbv the least of 8 / 16 / 32 that holds an instance's folds.  It reads the
+ * environment per call, like both entry points: FTMI_WR_NI=1 forces one instance
+ * (FTMI_WR_STAMPS=1, the phase stamps, changes no launch).  *n_launches receives the count,
+ * launches[0 .. min(count, capacity)) the launches (capacity 0: the count alone).
+ * n_folds <= 0: FTMI_E_ARG. */
+int ftmi_wavernn_route(int32_t n_folds, ftmi_wr_launch *launches, int32_t capacity,
+                       int32_t *n_launches);
+
 /* generate's tail (:246-261) in float64: samples (B, L) -> mu-law decode
  * (DSP.decode_mu_law(y, n_classes, False), utils/dsp.py:156-161; n_classes a power of two)
  * -> batched: xfade_and_unfold (:343-406), else fold 0 -> [:wave_len] -> the last fade_len
@@ -870,7 +888,7 @@ typedef struct {
  *                 g0 < 0, g0 >= n_rows, n_rows <= 0, out_row outside [0, n_out_rows), rows
  *                 past n_mel_rows / bias_row) and the table is copied in stream order; it
  *                 must stay unchanged until the stream has passed the call.
- *   launch_steps  host array, one entry per launch (ceil(n_folds / 32)), 1 .. L: the steps
+ *   launch_steps  host array, one entry per launch (ftmi_wavernn_route's count), 1 .. L: the steps
  *                 that launch runs (rows of unequal length: its longest row); NULL: L each.
  *   L             row stride of xin / samples / logits and the default step count
  *   n_out_rows, n_mel_rows, bias_row   rows of samples, of mel, and cond's last row. */
@@ -887,10 +905,18 @@ typedef struct {
   int32_t rnn_dims, fc_dims, feat_dims, aux_dims;
 } ftmi_wavernn_packed_args;
 
-/* ftmi_wavernn's launches (<= 32 folds each in table order, two instances from two folds on,
- * the same kernels and hand-off protocol) over a descriptor table.  Nothing is launched
- * when an argument or a host table row is refused. */
+/* ftmi_wavernn's launches (ftmi_wavernn_route(n_folds), in table order; the same kernels and
+ * hand-off protocol) over a descriptor table.  Nothing is launched when an argument or a
+ * host table row is refused. */
 int ftmi_wavernn_packed(const ftmi_wavernn_packed_args *args, ftmi_stream_t stream);
+
+/* Host-only: the row check ftmi_wavernn_packed makes on a host table, for a caller that
+ * hands its table over as device memory.  folds: n_folds rows in HOST memory; the other
+ * arguments are the ftmi_wavernn_packed_args fields of the same names.  FTMI_OK, or
+ * FTMI_E_SHAPE with the index of the first refused row in *bad_row (may be NULL);
+ * folds == NULL, n_folds <= 0 or hop <= 0: FTMI_E_ARG. */
+int ftmi_wr_check_folds(const ftmi_wr_fold *folds, int32_t n_folds, int32_t L, int32_t n_out_rows,
+                        int32_t n_mel_rows, int32_t bias_row, int32_t hop, int32_t *bad_row);
 
 /* One utterance of a packed sample matrix: its fold rows [first_row, first_row + n_folds),
  * its wave of wave_len float64 samples at out + out_offset. */
@@ -907,6 +933,15 @@ int ftmi_wr_unfold_packed(const float *samples, int32_t n_rows, int32_t L, const
                           int32_t n_items, int32_t target, int32_t overlap, int32_t batched,
                           int32_t mu_law, int32_t n_classes, int32_t fade_len, double *out,
                           int64_t out_len, ftmi_stream_t stream);
+
+/* Host-only: the row check ftmi_wr_unfold_packed makes on a host table (the shape rules of
+ * ftmi_wr_unfold, which is the single item (0, B, wave_len, 0) with out_len = wave_len;
+ * unbatched it reads fold 0 alone: n_folds = 1).  items: n_items rows in HOST memory; the
+ * other arguments as in ftmi_wr_unfold_packed.  FTMI_OK, or FTMI_E_SHAPE with the index of
+ * the first refused row in *bad_row (may be NULL); items == NULL or n_items <= 0: FTMI_E_ARG. */
+int ftmi_wr_check_items(const ftmi_wr_item *items, int32_t n_items, int32_t n_rows, int32_t L,
+                        int32_t target, int32_t overlap, int32_t batched, int32_t fade_len,
+                        int64_t out_len, int32_t *bad_row);
 
 /* ---- Tacotron decoder loop (models/tacotron.py; gen_tacotron.py, train_tacotron.py's
  * attention pass) ---------------------------------------------------------------------------

@@ -100,7 +100,8 @@ def main():
     loop_each = [device_ms(lambda m=m, s=s: voc.generate_samples(m, True, TARGET, OVERLAP, seed=s))
                  for m, s in zip(ms, seeds)]
     loop_packed = device_ms(lambda: voc.generate_samples_batch(ms, True, TARGET, OVERLAP, seeds=seeds))
-    launches_each = [-(-f // 32) for f in folds]
+    from forwardtacotron_amd import ops
+    launches_each = [len(ops.wavernn_route(f)) for f in folds]
     t1, tp = min(runs['one_by_one']), min(runs['packed'])
     row = {
         'workload': f'{len(ms)} synthetic mels of {T_MIN}-{T_MAX} frames, default config (hop '
