@@ -22,7 +22,8 @@ _lib = None
 c_int, c_int64, c_float, c_void_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 P = c_void_p  # every device pointer travels as void*
 # 22 still: ftmi_wavernn_packed, ftmi_wr_unfold_packed and the host-only queries
-# ftmi_wavernn_route, ftmi_wr_check_folds, ftmi_wr_check_items are new symbols; no existing
+# ftmi_wavernn_route, ftmi_wr_check_folds, ftmi_wr_check_items, and the length-aware batch's
+# ftmi_fill_tail, ftmi_maxpool_rows, ftmi_duration_counts_rows are new symbols; no existing
 # signature or struct changed, so a caller built against the earlier 22 keeps working (the
 # version is bumped on a signature change, include/ftmi.h)
 ABI_VERSION = 22
@@ -182,6 +183,9 @@ SIGNATURES = {
     'ftmi_duration_counts': (c_int, [P, c_int, c_int, c_int, c_float, P, P, P, P]),
     'ftmi_duration_trunc_sum': (c_int, [P, c_int, c_int, P, P]),
     'ftmi_duration_counts_global': (c_int, [P, c_int, c_int, P, c_float, P, P, P, P]),
+    'ftmi_fill_tail': (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, c_float, c_int, P]),
+    'ftmi_maxpool_rows': (c_int, [P, c_int64, c_int, c_int, c_int, P, P, c_int64, P]),
+    'ftmi_duration_counts_rows': (c_int, [P, c_int, c_int, P, c_int, c_float, P, P, P, P]),
     'ftmi_lr_index': (c_int, [P, c_int, c_int, c_int, P, P]),
     'ftmi_length_regulate': (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, P, c_int64, P]),
     'ftmi_series_proj_add': (c_int, [P, c_int64, c_int, c_int, c_int, P, P, P, c_float, P, P, P,

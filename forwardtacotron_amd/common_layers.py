@@ -309,8 +309,10 @@ class CBHG(Packed):
         img = ops.bank_halves_image(bank3, self.K, ws[0].size(1), self.channels)
         return bank_w, scale, shift, w_pre, bank3, presplit(w_pre), img
 
-    def forward_cl(self, x: torch.Tensor) -> torch.Tensor:
-        """(B, T, Cin) channels-last -> (B, T, 2*channels)."""
+    def forward_cl(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(B, T, Cin) channels-last -> (B, T, 2*channels).  lengths: (B,) int32 on the device
+        — item b holds lengths[b] valid rows and its result on them is that of the item
+        alone (see _after_bank); x must then be zero in the K // 2 rows past each item's end."""
         bank_w, scale, shift, w_pre, bank3, pre3, img = self.packed_weights()
         pooled = ops.bank_pools(x, self.K, self.channels, w_split=bank3)
         # pooled: the bank kernel applied the maxpool, and (split) stored its output as the
@@ -320,7 +322,7 @@ class CBHG(Packed):
         bank = ops.conv_bank(ops.split_rows(x) if xin else x, bank_w, self.K, self.channels,
                              scale, shift, w_split=bank3, pool=pooled, split_out=split,
                              x_split=xin, w_image=img)
-        return self._after_bank(bank, x, pooled, split)
+        return self._after_bank(bank, x, pooled, split, lengths)
 
     def embed_bank_table(self, embedding_weight: torch.Tensor) -> torch.Tensor:
         """The conv bank folded through an embedding (ops.embed_bank_table: [S][K(K+1)/2]
@@ -331,43 +333,59 @@ class CBHG(Packed):
         return cached_pack(self, '_ftmi_embed_table', lambda: ops.embed_bank_table(
             w, [c.conv.weight for c in self.conv1d_bank]), (w.data_ptr(), w._version, w.device))
 
-    def forward_ids(self, x_ids: torch.Tensor, embedding_weight: torch.Tensor) -> torch.Tensor:
+    def forward_ids(self, x_ids: torch.Tensor, embedding_weight: torch.Tensor,
+                    lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """forward_cl(embedding(x_ids)): (B, T) ids -> (B, T, 2*channels).  From
         ops.EMBED_BANK_MIN_ROWS rows on the conv bank is a gather of `embed_bank_table` rows
         (ops.embed_bank) instead of a GEMM over the embedded rows, which then only serve as
-        the proj2 residual."""
+        the proj2 residual.  lengths: as in forward_cl; the ids from lengths[b] on must then
+        lie outside the table (they embed to zero rows in both forms of the bank)."""
         w = embedding_weight.detach()
         h = ops.embedding(x_ids, w)
         # shapes without a table kernel (ops.embed_bank_ok) keep the GEMM bank, like few rows
         if (x_ids.numel() < ops.EMBED_BANK_MIN_ROWS
                 or w.size(1) != self.conv1d_bank[0].conv.in_channels
                 or not ops.embed_bank_ok(w.size(0), 1, self.K, self.channels)):
-            return self.forward_cl(h)
+            return self.forward_cl(h, lengths)
         _, scale, shift, _, bank3 = self.packed_weights()[:5]
         # split rows exactly where forward_cl's pooled bank would store them (proj1 then reads
         # them on the f16x3 slab kernel); fp32 rows elsewhere and under ops.exact_paths()
         split = ops.SPLIT_ROWS and ops.bank_pools(h, self.K, self.channels, w_split=bank3)
         bank = ops.embed_bank(x_ids, self.embed_bank_table(w), 1, self.K, self.channels, scale,
                               shift, pool=True, split_out=split)
-        return self._after_bank(bank, h, True, split)
+        return self._after_bank(bank, h, True, split, lengths)
 
     def _after_bank(self, bank: torch.Tensor, x: torch.Tensor, pooled: bool,
-                    split: bool) -> torch.Tensor:
+                    split: bool, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """proj1 -> proj2 + residual x -> highways -> GRU on the bank output (pooled: the
-        maxpool already applied; split: stored as f16x3 split rows)."""
+        maxpool already applied; split: stored as f16x3 split rows).
+        lengths (None: the launches are exactly those without it): item b ends at row
+        lengths[b].  proj1 and proj2 (k = 3) read one row past an item's end, which the item
+        alone sees as zero padding: that row of the pooled bank output and of proj1's output
+        is zeroed (ops.fill_tail; a bank that is not pooled yet is pooled by
+        ops.maxpool_rows, which also writes the zero rows, since no row of the unpooled
+        bank can make max(bank[L-1], bank[L]) zero).  The layers after proj2 are pointwise,
+        and the GRU takes the lengths (pack_padded_sequence semantics)."""
         bank_w, scale, shift, w_pre, bank3, pre3, img = self.packed_weights()
+        if lengths is not None:
+            if pooled:
+                ops.fill_tail(bank, lengths, reach=1, split=bool(split))
+            else:
+                bank, pooled = ops.maxpool_rows(bank, lengths), True
         y = self.conv_project1.forward_cl(bank, maxpool=not pooled, x_split=split)
         del bank
+        if lengths is not None:
+            ops.fill_tail(y, lengths, reach=1)
         y = self.conv_project2.forward_cl(y, residual=x)
         xp = self._highway_stack(y)
         if xp is not None:
-            return self.rnn.recur(xp)
+            return self.rnn.recur(xp, lengths=lengths)
         h, _ = ops.conv1d(y, w_pre, 1, 0, w_split=pre3)
         h2 = torch.empty_like(h)
         for hw in self.highways:
             hw.forward_cl(h, out=h2)
             h, h2 = h2, h
-        return self.rnn.forward_cl(h)
+        return self.rnn.forward_cl(h, lengths=lengths)
 
     def _stack_pack(self):
         """Fragment-major f16x3 blocks of pre_highway, the highways' w12 and the GRU's W_ih

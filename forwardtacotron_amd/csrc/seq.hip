@@ -338,6 +338,208 @@ extern "C" int ftmi_rowdot(const float *x, int64_t x_stride, int64_t M, int32_t 
   return FTMI_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// Length-aware batches (ForwardTacotron.generate_masked): every item starts at row 0 of its
+// own batch row, so only its right edge differs from the item run alone.  The kernels below
+// restore that edge: a constant in the rows a conv reads past an item's end, the CBHG
+// maxpool with such an end, and the duration rules decided per item.
+namespace {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// rows [len[b], min(T, len[b] + n_reach)) of a (B, T, C) operand: one wave per tail row.
+// A row is C 32-bit words, w0 below word `split` and w1 from it on (fp32 rows: split = C;
+// f16x3 split rows: C / 2 words of head pairs, then C / 2 words of tail pairs).  vec: C,
+// split and the stride are multiples of 4 words and x is 16-byte aligned.
+__global__ __launch_bounds__(256) void fill_tail_rows_kernel(
+    uint32_t *x, int64_t stride, int B, int T, int C, const int32_t *__restrict__ len,
+    int n_reach, uint32_t w0, uint32_t w1, int split, int vec) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= (int64_t)B * n_reach) return;
+  const int b = (int)(r / n_reach), j = (int)(r - (int64_t)b * n_reach);
+  int L = len[b];
+  if (L < 0) L = 0;
+  const int64_t t = (int64_t)L + j;
+  if (t >= T) return;  // row T is the next item's row 0
+  uint32_t *row = x + ((int64_t)b * T + t) * stride;
+  if (vec) {
+    const u32x4 v0 = {w0, w0, w0, w0}, v1 = {w1, w1, w1, w1};
+    for (int q = lane; q < C / 4; q += 64) ((u32x4 *)row)[q] = 4 * q < split ? v0 : v1;
+  } else {
+    for (int c = lane; c < C; c += 64) row[c] = c < split ? w0 : w1;
+  }
+}
+
+// the same tail of a time-last (B, C, T) operand (channel stride cstride >= T): one thread
+// per element, consecutive threads on consecutive frames
+__global__ __launch_bounds__(256) void fill_tail_tlast_kernel(
+    float *x, int64_t cstride, int B, int C, int T, const int32_t *__restrict__ len,
+    int n_reach, float value) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)B * C * n_reach) return;
+  const int64_t bc = i / n_reach;
+  const int j = (int)(i - bc * n_reach);
+  int L = len[bc / C];
+  if (L < 0) L = 0;
+  const int64_t t = (int64_t)L + j;
+  if (t >= T) return;
+  x[bc * cstride + t] = value;
+}
+
+// CBHG maxpool (MaxPool1d(2, 1, padding=1)[..., :T]: y[t] = max(x[t-1], x[t]), x[-1] = -inf)
+// of each item up to its length, zero rows from there on: one wave per row, float4 lanes
+__global__ __launch_bounds__(256) void maxpool_rows_kernel(
+    const float *__restrict__ x, int64_t x_stride, int B, int T, int C4,
+    const int32_t *__restrict__ len, float *__restrict__ y, int64_t y_stride) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= (int64_t)B * T) return;
+  const int b = (int)(r / T), t = (int)(r - (int64_t)b * T);
+  const bool valid = t < len[b];
+  const f32x4 *cur = (const f32x4 *)(x + r * x_stride);
+  const f32x4 *prev = (const f32x4 *)(x + (r - 1) * x_stride);
+  f32x4 *yd = (f32x4 *)(y + r * y_stride);
+  for (int q = lane; q < C4; q += 64) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (valid) {
+      v = cur[q];
+      if (t > 0) {
+        const f32x4 p = prev[q];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(p[e], v[e]);
+      }
+    }
+    yd[q] = v;
+  }
+}
+
+// duration_counts_kernel with per-item lengths: one wave per row.  Positions from x_len[b]
+// on get duration 0 and count 0; the fill-2 rule is decided on the row's own valid
+// positions (generate() of the item alone); clip, count and scan as in the kernel above.
+__global__ __launch_bounds__(256) void duration_counts_rows_kernel(
+    float *dur, int B, int T, const int32_t *__restrict__ x_len, int apply_fill, float fill,
+    int32_t *offsets, int32_t *totals, int32_t *fill_flags) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  float *row = dur + (int64_t)b * T;
+  int32_t *off = offsets + (int64_t)b * (T + 1);
+  int L = x_len[b];
+  L = L < 0 ? 0 : (L > T ? T : L);
+  int filled = 0;
+  if (apply_fill) {
+    long long acc = 0;
+    for (int t = lane; t < L; t += 64) acc += (long long)row[t];  // trunc toward 0
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    acc = __shfl(acc, 0, 64);
+    filled = acc <= 0;
+  }
+  if (fill_flags && lane == 0) fill_flags[b] = filled;
+  int carry = 0;
+  for (int t0 = 0; t0 < T; t0 += 64) {
+    const int t = t0 + lane;
+    int c = 0;
+    if (t < L) {
+      float d = row[t];
+      if (filled) {
+        d = fill;
+        row[t] = d;
+      }
+      if (d < 0.f) {
+        d = 0.f;
+        row[t] = d;
+      }
+      const float s = __fadd_rn(d, 0.5f);
+      c = (int)s;  // truncation, as torch .long()
+    } else if (t < T) {
+      row[t] = 0.f;
+    }
+    int incl = c;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += v;
+    }
+    if (t < T) off[t] = carry + incl - c;
+    carry += __shfl(incl, 63, 64);
+  }
+  if (lane == 0) {
+    off[T] = carry;
+    totals[b] = carry;
+  }
+}
+
+}  // namespace
+
+extern "C" int ftmi_fill_tail(float *x, int64_t stride, int32_t B, int32_t T, int32_t C,
+                              const int32_t *len, int32_t reach, float value, int32_t mode,
+                              ftmi_stream_t stream) {
+  if (!x || !len || B <= 0 || T <= 0 || C <= 0) return FTMI_E_ARG;
+  if (mode != FTMI_FILL_ROWS && mode != FTMI_FILL_TIME_LAST && mode != FTMI_FILL_SPLIT_ROWS)
+    return FTMI_E_ARG;
+  if (stride < (mode == FTMI_FILL_TIME_LAST ? T : C)) return FTMI_E_SHAPE;
+  if (mode == FTMI_FILL_SPLIT_ROWS && C % 2) return FTMI_E_SHAPE;
+  if (reach == 0) return FTMI_OK;
+  const int n_reach = reach < 0 || reach > T ? T : reach;
+  if (mode == FTMI_FILL_TIME_LAST) {
+    const int64_t blocks = ((int64_t)B * C * n_reach + 255) / 256;
+    if (blocks > 0x7fffffff) return FTMI_E_UNSUPPORTED;
+    hipLaunchKernelGGL(fill_tail_tlast_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                       ftmi_hs(stream), x, stride, B, C, T, len, n_reach, value);
+    FTMI_CHECK_LAUNCH();
+    return FTMI_OK;
+  }
+  uint32_t w0, w1;
+  int split = C;
+  memcpy(&w0, &value, 4);
+  w1 = w0;
+  if (mode == FTMI_FILL_SPLIT_ROWS) {  // include/ftmi.h: heads f16(v), tails f16((v - h) 2^11)
+    const _Float16 h = (_Float16)value;
+    const _Float16 tl = (_Float16)((value - (float)h) * 2048.f);
+    uint16_t hb, tb;
+    memcpy(&hb, &h, 2);
+    memcpy(&tb, &tl, 2);
+    w0 = (uint32_t)hb | ((uint32_t)hb << 16);
+    w1 = (uint32_t)tb | ((uint32_t)tb << 16);
+    split = C / 2;
+  }
+  const int vec = C % 4 == 0 && split % 4 == 0 && !(stride & 3) && ftmi_aligned16(x);
+  const int64_t blocks = ((int64_t)B * n_reach + 3) / 4;
+  if (blocks > 0x7fffffff) return FTMI_E_UNSUPPORTED;
+  hipLaunchKernelGGL(fill_tail_rows_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     ftmi_hs(stream), (uint32_t *)x, stride, B, T, C, len, n_reach, w0, w1, split,
+                     vec);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_maxpool_rows(const float *x, int64_t x_stride, int32_t B, int32_t T,
+                                 int32_t C, const int32_t *len, float *y, int64_t y_stride,
+                                 ftmi_stream_t stream) {
+  if (!x || !len || !y || B <= 0 || T <= 0 || C <= 0) return FTMI_E_ARG;
+  if (x_stride < C || y_stride < C) return FTMI_E_SHAPE;
+  if (C % 4 || (x_stride & 3) || (y_stride & 3)) return FTMI_E_ALIGN;
+  if (!ftmi_aligned16(x) || !ftmi_aligned16(y)) return FTMI_E_ALIGN;
+  const int64_t blocks = ((int64_t)B * T + 3) / 4;
+  if (blocks > 0x7fffffff) return FTMI_E_UNSUPPORTED;
+  hipLaunchKernelGGL(maxpool_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ftmi_hs(stream),
+                     x, x_stride, B, T, C / 4, len, y, y_stride);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
+}
+
+extern "C" int ftmi_duration_counts_rows(float *dur, int32_t B, int32_t T, const int32_t *x_len,
+                                         int32_t apply_fill, float fill_value, int32_t *offsets,
+                                         int32_t *totals, int32_t *fill_flags,
+                                         ftmi_stream_t stream) {
+  if (!dur || !x_len || !offsets || !totals || B <= 0 || T <= 0) return FTMI_E_ARG;
+  hipLaunchKernelGGL(duration_counts_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0,
+                     ftmi_hs(stream), dur, B, T, x_len, apply_fill, fill_value, offsets, totals,
+                     fill_flags);
+  FTMI_CHECK_LAUNCH();
+  return FTMI_OK;
+}
+
 extern "C" int ftmi_abi_version(void) { return 22; }
 
 static int g_cu_limit = 0;

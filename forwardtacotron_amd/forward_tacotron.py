@@ -90,9 +90,52 @@ class SeriesPredictor(Packed):
         w, b = self.packed_weights()
         return ops.rowdot(h, w, b, alpha)
 
+    def forward_masked(self, ids: torch.Tensor, lengths: torch.Tensor,
+                       alpha: float = 1.0) -> torch.Tensor:
+        """_forward_ops for items of unequal length: (B, T) ids whose positions from
+        lengths[b] on lie outside the table (zero embedded rows), lengths (B,) int32 on the
+        device -> (B, T) series, on each item's valid positions what forward_bt gives for
+        the item alone (the pad positions hold no defined value).  Convs 2 and 3 (k = 5)
+        read two rows past an item's end: those rows of their inputs are zeroed, and the
+        GRU takes the lengths."""
+        h = ops.embedding(ids, self.embedding.weight.detach())
+        for i, conv in enumerate(self.convs):
+            h = conv.forward_cl(h)
+            if i + 1 < len(self.convs):
+                ops.fill_tail(h, lengths, reach=self.convs[i + 1].kernel // 2)
+        h = self.rnn.forward_cl(h, lengths=lengths)
+        w, b = self.packed_weights()
+        return ops.rowdot(h, w, b, alpha)
+
     def forward(self, x: torch.Tensor, alpha: float = 1.0) -> torch.Tensor:
         """(B, T) -> (B, T, 1), like the reference."""
         return self.forward_bt(x, alpha).unsqueeze(-1)
+
+
+PAD_ID = -1  # a pad position of a length-aware batch: outside every table, embeds to zero
+
+
+def batch_plan(lengths, max_batch=None):
+    """Chunk plan of generate_batch (host only).  lengths: the items' token counts, in input
+    order.  Returns (chunks, inverse): chunks is a list of lists of input positions, each of
+    at most max_batch items, taken from the items sorted by length (longest first, ties in
+    input order) so a chunk pads little; max_batch=None is one chunk in input order.
+    inverse[i] is the place of input item i in the concatenation of the chunks, so
+    [flat[inverse[i]] for i in range(n)] restores input order."""
+    n = len(lengths)
+    if n == 0:
+        raise ValueError('xs: no sequences given')
+    if max_batch is None:
+        chunks = [list(range(n))]
+    else:
+        if int(max_batch) < 1:
+            raise ValueError(f'max_batch must be at least 1 (got {max_batch})')
+        order = sorted(range(n), key=lambda i: (-int(lengths[i]), i))
+        chunks = [order[i:i + int(max_batch)] for i in range(0, n, int(max_batch))]
+    inverse = [0] * n
+    for pos, i in enumerate(i for c in chunks for i in c):
+        inverse[i] = pos
+    return chunks, inverse
 
 
 class ForwardTacotron(nn.Module):
@@ -430,6 +473,163 @@ class ForwardTacotron(nn.Module):
                     ent['done'].record(torch.cuda.current_stream(x.device))
                 return out
         return ops.run_checked(run, x.device, reduce=None if batch is None else batch.status)
+
+    # ---------------------------------------------------------------------------------
+    # length-aware batches: each item's result is that of generate() on the item alone
+
+    def _masked_pass(self, ids, lens, alpha, pitch_fn, energy_fn):
+        """One length-aware pass.  ids: (B, T) int64 on the device, PAD_ID
+        from lens[b] on; lens: (B,) int32 on the device.  Every item starts at row 0 of its
+        batch row, so the existing kernels give its left edge; at its right edge the rows a
+        conv reads past the end are zeroed (ops.fill_tail), the recurrences take the lengths,
+        and the duration rules are decided per item.  One launch per op, all on the caller's
+        stream (no side streams: nothing to co-schedule).  Returns (dict, totals on the
+        host); the one host sync is the copy of the totals."""
+        dev = ids.device
+        B = ids.size(0)
+        dur = self.dur_pred.forward_masked(ids, lens, alpha)
+        offsets, totals, _ = ops.duration_counts_rows(dur, lens)
+        t_host = torch.empty(B, dtype=torch.int32, pin_memory=True)
+        t_host.copy_(totals, non_blocking=True)
+        t_ready = torch.cuda.Event()
+        t_ready.record(torch.cuda.current_stream(dev))
+        series = []
+        for pred, fn in ((self.pitch_pred, pitch_fn), (self.energy_pred, energy_fn)):
+            s = pred.forward_masked(ids, lens).unsqueeze(1)
+            ops.fill_tail(s, lens, time_last=True)  # the callback sees zero pads ...
+            s = fn(s)
+            if s.dtype != torch.float32 or not s.is_contiguous():
+                s = s.float().contiguous()
+            ops.fill_tail(s, lens, time_last=True)  # ... and whatever it wrote there goes
+            series.append(s)
+        pitch, energy = series
+        enc = self.prenet.forward_ids(ids, self.embedding.weight, lengths=lens)
+        xp = self.lstm.project(enc)
+        del enc
+        wp, bp, we, be = self._folded_series_weights()
+        ops.series_proj_add(xp, pitch, wp, bp, self.pitch_strength, energy, we, be,
+                            self.energy_strength)
+        t_ready.synchronize()
+        tot = t_host.clone()
+        T_mel = int(tot.max())
+        index = ops.lr_index(offsets, T_mel)
+        # the decoder of forward(): frames past an item's total are skipped by the LSTM (zero
+        # rows, so lin leaves its bias there, not lin(padding_value))
+        lstm_out = self.lstm.recur(xp, T=T_mel, index=index, lengths=totals, pad_value=0.0)
+        del xp
+        mel_cl = torch.empty(B, T_mel, self.n_mels, device=dev)
+        mel = torch.empty(B, self.n_mels, T_mel, device=dev)
+        w, b, w3 = self.lin.packed_weights()
+        ops.conv1d(lstm_out, w, 1, 0, bias=b, out=mel_cl, out_t=mel, w_split=w3)
+        del lstm_out
+        ops.fill_tail(mel_cl, totals, reach=self.postnet.K // 2)  # the bank's input and residual
+        ops.fill_tail(mel, totals, value=self.padding_value, time_last=True)
+        post = self.postnet.forward_cl(mel_cl, lengths=totals)
+        mel_post = torch.empty(B, self.n_mels, T_mel, device=dev)
+        w, _, w3 = self.post_proj.packed_weights()
+        ops.conv1d(post, w, 1, 0, out_t=mel_post, want_y=False, w_split=w3)
+        ops.fill_tail(mel_post, totals, value=self.padding_value, time_last=True)
+        return {'mel': mel, 'mel_post': mel_post, 'dur': dur, 'pitch': pitch,
+                'energy': energy, 'mel_len': tot.to(torch.int64)}, tot
+
+    def _run_masked(self, ids, lens, alpha, pitch_fn, energy_fn):
+        """_masked_pass under the f16x3 range guard.  The rows past an item's halo hold
+        finite values nobody reads for a valid row; they still pass through the f16x3 GEMMs
+        and may set the range bit, and the pass then runs again on the fp32 paths."""
+        if self.training:
+            self.eval()
+
+        def run():
+            with torch.no_grad():
+                return self._masked_pass(ids, lens, alpha, pitch_fn, energy_fn)
+        return ops.run_checked(run, ids.device)
+
+    def generate_masked(self,
+                        x: torch.Tensor,
+                        x_len,
+                        alpha=1.0,
+                        pitch_function: Callable[[torch.Tensor], torch.Tensor] = _identity,
+                        energy_function: Callable[[torch.Tensor], torch.Tensor] = _identity
+                        ) -> Dict[str, torch.Tensor]:
+        """generate() of a padded batch whose items do not see each other or the padding.
+        x: (B, T) int64 on the model's device; x_len: (B,) lengths in [1, T] (a tensor on
+        either side or a sequence; read on the host).  Whatever x holds from x_len[b] on is
+        ignored (an id 0 below x_len[b] is a real symbol).  Returns generate()'s dictionary
+        for the batch plus 'mel_len' ((B,) int64 on the host: each item's frame count):
+        item b's `mel` / `mel_post` frames below mel_len[b] and `dur` / `pitch` / `energy`
+        positions below x_len[b] are what generate(x[b:b+1, :x_len[b]]) returns; past them
+        mel / mel_post hold padding_value and dur / pitch / energy hold 0.
+        The callbacks get the padded (B, 1, T) series once, pads zeroed before the call and
+        again after it; equality with the item alone is promised for elementwise callbacks."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.size(0) < 1 or x.size(1) < 1:
+            raise ValueError('x: a (B, T) tensor of token ids is expected, got '
+                             + (f'shape {tuple(x.shape)}' if isinstance(x, torch.Tensor)
+                                else type(x).__name__))
+        B, T = x.shape
+        lens = torch.as_tensor(x_len.cpu() if isinstance(x_len, torch.Tensor) else x_len)
+        if lens.dim() != 1 or lens.numel() != B:
+            raise ValueError(f'x_len: {B} lengths expected for x of shape {(B, T)}, got shape '
+                             f'{tuple(lens.shape)}')
+        if lens.is_floating_point() or int(lens.min()) < 1 or int(lens.max()) > T:
+            raise ValueError(f'x_len: integer lengths in [1, T = {T}] expected, got '
+                             f'{lens.tolist()}')
+        if not x.is_cuda:
+            raise RuntimeError('x: generate_masked runs on a HIP device only (got a CPU '
+                               'tensor); there is no CPU path')
+        self._check_device(x)
+        lens = lens.to(torch.int32).to(x.device)
+        pad = torch.arange(T, device=x.device).unsqueeze(0) >= lens.unsqueeze(1)
+        ids = x.long().masked_fill(pad, PAD_ID)
+        return self._run_masked(ids, lens, alpha, pitch_function, energy_function)[0]
+
+    def generate_batch(self,
+                       xs,
+                       alpha=1.0,
+                       pitch_function: Callable[[torch.Tensor], torch.Tensor] = _identity,
+                       energy_function: Callable[[torch.Tensor], torch.Tensor] = _identity,
+                       max_batch=None):
+        """Synthesise many sentences of unequal length in shared launches.  xs: a list of 1-D
+        token tensors or int lists.  Returns a list of dictionaries in input order, item i's
+        the one generate(x_i[None]) returns — 'mel' / 'mel_post' (1, n_mels, T_mel_i), 'dur'
+        (1, L_i), 'pitch' / 'energy' (1, 1, L_i) — each tensor with storage of its own.
+        max_batch: items are sorted by length and run in chunks of at most that many
+        (batch_plan; results do not depend on batch-mates, so the order is free).  The
+        callbacks run once per chunk, see generate_masked."""
+        if isinstance(xs, torch.Tensor) or not hasattr(xs, '__len__'):
+            raise ValueError('xs: a list of 1-D token sequences is expected')
+        if len(xs) == 0:
+            raise ValueError('xs: no sequences given')
+        seqs = []
+        for i, s in enumerate(xs):
+            a = np.asarray(s.detach().cpu() if isinstance(s, torch.Tensor) else s)
+            if a.ndim != 1 or a.size == 0:
+                raise ValueError(f'xs[{i}]: a non-empty 1-D token sequence is expected, got '
+                                 f'shape {a.shape}')
+            if a.dtype.kind not in 'iu':
+                raise ValueError(f'xs[{i}]: integer token ids expected, got {a.dtype}')
+            seqs.append(a.astype(np.int64))
+        chunks, inverse = batch_plan([a.size for a in seqs], max_batch)
+        dev = self.embedding.weight.device
+        if not self.embedding.weight.is_cuda:
+            raise RuntimeError('forwardtacotron_amd.ForwardTacotron runs on a HIP device only: '
+                               'call model.to("cuda") first (there is no CPU path)')
+        flat = []
+        for chunk in chunks:
+            lens = [seqs[i].size for i in chunk]
+            ids = np.full((len(chunk), max(lens)), PAD_ID, dtype=np.int64)
+            for r, i in enumerate(chunk):
+                ids[r, :lens[r]] = seqs[i]
+            out, tot = self._run_masked(torch.from_numpy(ids).to(dev),
+                                        torch.tensor(lens, dtype=torch.int32).to(dev), alpha,
+                                        pitch_function, energy_function)
+            for r, L in enumerate(lens):
+                F = int(tot[r])
+                flat.append({'mel': out['mel'][r:r + 1, :, :F].clone(),
+                             'mel_post': out['mel_post'][r:r + 1, :, :F].clone(),
+                             'dur': out['dur'][r:r + 1, :L].clone(),
+                             'pitch': out['pitch'][r:r + 1, :, :L].clone(),
+                             'energy': out['energy'][r:r + 1, :, :L].clone()})
+        return [flat[p] for p in inverse]
 
     def __prepare_scriptable__(self):
         """`torch.jit.script(model)` (the reference's export, README.md:149-161): the compute

@@ -4,7 +4,9 @@ phonemizer — is absent from this image, so raw English text is refused with th
 
     python -m forwardtacotron_amd.gen_forward [--checkpoint ckpt.pt | --config config.yaml] \\
         [--input_phonemes "həloʊ wɜːld" | --input_tokens 12,40,7 | --sentences file] \\
-        [--alpha 1.0] [--amp 1.0] {griffinlim,melgan,hifigan,wavernn}
+        [--alpha 1.0] [--amp 1.0] [--batch N] {griffinlim,melgan,hifigan,wavernn}
+                          (--batch N > 1: up to N sentences share the acoustic model's
+                           launches, ForwardTacotron.generate_batch; the same files)
     python -m forwardtacotron_amd.gen_forward ... wavernn \\
         [--voc_checkpoint voc.pt | --voc_synthetic] [--target 11000] [--overlap 550] \\
         [--voc_batch N]   (N > 1: up to N sentences' mels vocoded by one
@@ -193,6 +195,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--alpha', type=float, default=1.)
     parser.add_argument('--amp', type=float, default=1.)
     parser.add_argument('--out', default='model_outputs')
+    parser.add_argument('--batch', default=1, type=int,
+                        help='[int] sentences synthesised together (generate_batch: each '
+                             "sentence's mel is that of the sentence alone); 1: one at a time")
     subparsers = parser.add_subparsers(dest='vocoder')
     wr_parser = subparsers.add_parser('wavernn')
     wr_parser.add_argument('--overlap', '-o', default=550, type=int,
@@ -264,6 +269,28 @@ def main(argv: Optional[Sequence[str]] = None) -> List[Path]:
             written.append(p)
         pending.clear()
 
+    batch = getattr(args, 'batch', 1)
+    if batch < 1:
+        raise SystemExit('--batch must be at least 1')
+    if batch > 1:
+        # sentences synthesised together (ForwardTacotron.generate_batch: each one's mel is
+        # the mel of the sentence alone), in chunks of at most `batch`; the outputs are then
+        # written in the original numbering, like the loop below
+        print(f'\n| Generating {len(texts)} sentences in batches of up to {batch}')
+        gens = tts_model.generate_batch(texts, alpha=args.alpha, pitch_function=pitch_function,
+                                        energy_function=energy_function, max_batch=batch)
+        for i, gen in enumerate(gens, 1):
+            name = wav_name(i, tts_k, args.alpha, args.amp, args.vocoder)
+            if voc_batch > 1:  # generate_batch gave every mel storage of its own
+                pending.append((name, gen['mel_post']))
+                if len(pending) == voc_batch or i == len(texts):
+                    flush()
+                continue
+            m = d2h.fetch(gen['mel_post'])
+            written.append(write_output(m, name, args.vocoder, out_path, dsp, voc,
+                                        getattr(args, 'target', 11000),
+                                        getattr(args, 'overlap', 550), mel_dev=gen['mel_post']))
+        texts = []
     for i, ids in enumerate(texts, 1):
         print(f'\n| Generating {i}/{len(texts)}')
         x = torch.as_tensor(ids, dtype=torch.long, device=device).unsqueeze(0)

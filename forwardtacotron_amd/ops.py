@@ -838,6 +838,76 @@ def duration_counts_global(dur: torch.Tensor, global_sum: torch.Tensor, fill_val
     return offsets, totals, flag
 
 
+def _lens(lengths: torch.Tensor, B: int, device) -> torch.Tensor:
+    """Per-item lengths as the kernels take them: device int32 [B], contiguous."""
+    if lengths.numel() != B:
+        raise ValueError(f'lengths holds {lengths.numel()} values for a batch of {B}')
+    return lengths.to(device=device, dtype=torch.int32).contiguous()
+
+
+def duration_counts_rows(dur: torch.Tensor, x_len: torch.Tensor, apply_fill: bool = True,
+                         fill_value: float = 2.0):
+    """duration_counts decided per item (x_len: (B,) valid positions of each row).  In place:
+    duration 0 from x_len[b] on, the fill-2 rule on each row's own valid positions, the clip;
+    returns (offsets (B, T+1), totals (B,), fill_flags (B,))."""
+    _dev(dur, x_len)
+    if dur.dtype != _f32 or not dur.is_contiguous() or dur.dim() != 2:
+        raise ValueError('dur must be a contiguous (B, T) fp32 tensor')
+    B, T = dur.shape
+    x_len = _lens(x_len, B, dur.device)
+    offsets = torch.empty(B, T + 1, device=dur.device, dtype=torch.int32)
+    totals = torch.empty(B, device=dur.device, dtype=torch.int32)
+    flags = torch.empty(B, device=dur.device, dtype=torch.int32)
+    launch('ftmi_duration_counts_rows', f'duration_counts_rows[B={B},T={T}]', 0, B * T * 12,
+           dur.data_ptr(), B, T, x_len.data_ptr(), int(apply_fill), float(fill_value),
+           offsets.data_ptr(), totals.data_ptr(), flags.data_ptr(), _stream())
+    return offsets, totals, flags
+
+
+FILL_ROWS, FILL_TIME_LAST, FILL_SPLIT_ROWS = 0, 1, 2  # include/ftmi.h FTMI_FILL_*
+
+
+def fill_tail(x: torch.Tensor, lengths: torch.Tensor, reach: int = -1, value: float = 0.0,
+              time_last: bool = False, split: bool = False) -> torch.Tensor:
+    """In place: `value` in rows [lengths[b], min(T, lengths[b] + reach)) of every item of a
+    channels-last (B, T, C) view (reach < 0: the whole tail).  time_last: x is (B, C, T) with
+    unit frame stride; split: the rows hold f16x3 split rows (conv_bank(split_out=True))."""
+    _dev(x, lengths)
+    if time_last:
+        if split:
+            raise ValueError('fill_tail: split rows are channels-last')
+        # a single channel's stride is whatever the view says: the item stride counts
+        stride = x.stride(1) if x.dim() == 3 and x.size(1) > 1 else x.stride(0)
+        if (x.dim() != 3 or x.dtype != _f32 or x.stride(2) != 1
+                or x.stride(0) != x.size(1) * stride):
+            raise ValueError(f'fill_tail: expected a (B, C, T) fp32 view with unit frame stride '
+                             f'and uniform channel stride, got shape {tuple(x.shape)} strides '
+                             f'{x.stride()}')
+        B, C, T = x.shape
+        mode = FILL_TIME_LAST
+    else:
+        B, T, C, stride = _rows(x)
+        mode = FILL_SPLIT_ROWS if split else FILL_ROWS
+    lengths = _lens(lengths, B, x.device)
+    n = T if reach < 0 else min(reach, T)
+    launch('ftmi_fill_tail', f'fill_tail[B={B},T={T},C={C},reach={reach},mode={mode}]', 0,
+           4.0 * B * n * C, x.data_ptr(), stride, B, T, C, lengths.data_ptr(), int(reach),
+           float(value), mode, _stream())
+    return x
+
+
+def maxpool_rows(x: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+    """The CBHG maxpool of (B, T, C) rows whose items end at lengths[b]: max(x[t-1], x[t])
+    below it, zero rows from there on."""
+    _dev(x, lengths)
+    B, T, C, xs = _rows(x)
+    lengths = _lens(lengths, B, x.device)
+    y = torch.empty(B, T, C, device=x.device, dtype=_f32)
+    launch('ftmi_maxpool_rows', f'maxpool_rows[M={B * T},C={C}]', 0, 8.0 * B * T * C,
+           x.data_ptr(), xs, B, T, C, lengths.data_ptr(), y.data_ptr(), y.stride(1), _stream())
+    return y
+
+
 def lr_index(offsets: torch.Tensor, T_mel: int) -> torch.Tensor:
     _dev(offsets)
     B, T1 = offsets.shape

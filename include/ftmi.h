@@ -94,7 +94,8 @@ enum { FTMI_BANK_COUNTERS = 4096 };
  * 22: ftmi_rnn_route, ftmi_rnn_switches_digest; no existing signature changed;
  * added under 22 without a signature change: ftmi_frame_power, ftmi_trim_bounds, ftmi_peak_abs,
  * ftmi_prepare_audio; ftmi_wavernn_packed, ftmi_wr_unfold_packed; ftmi_wavernn_route,
- * ftmi_wr_check_folds, ftmi_wr_check_items). */
+ * ftmi_wr_check_folds, ftmi_wr_check_items; ftmi_fill_tail, ftmi_maxpool_rows,
+ * ftmi_duration_counts_rows). */
 int ftmi_abi_version(void);
 /* sha256 (hex) of the sources this library was built from (the .hip and .h files of
  * forwardtacotron_amd/csrc and include/ftmi.h): the Python binding refuses a library whose
@@ -490,6 +491,45 @@ int ftmi_duration_trunc_sum(const float *dur, int32_t B, int32_t T, int64_t *out
 int ftmi_duration_counts_global(float *dur, int32_t B, int32_t T, const int64_t *global_sum,
                                 float fill_value, int32_t *offsets, int32_t *totals,
                                 int32_t *fill_flag, ftmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Length-aware batches (ForwardTacotron.generate_masked): item b of a padded batch holds
+ * len[b] valid rows from row 0 on; these restore at its right edge what the item run alone
+ * would see.  len / x_len: device int32 [B]; a negative entry counts as 0.
+ *
+ * ftmi_fill_tail writes `value` to rows [len[b], min(T, len[b] + reach)) of every item
+ * (reach < 0: up to T; reach == 0 or len[b] >= T: nothing).  It never writes at or past row
+ * T of an item and never between C and the stride.  mode:
+ *   FTMI_FILL_ROWS        x is (B, T, C) fp32 rows, `stride` floats per row (>= C), item
+ *                         stride T * stride.  16-byte stores when C % 4 == 0, stride % 4 == 0
+ *                         and x is 16-byte aligned, 4-byte stores otherwise.
+ *   FTMI_FILL_TIME_LAST   x is (B, C, T), `stride` floats per channel (>= T), item stride
+ *                         C * stride; 4-byte stores.
+ *   FTMI_FILL_SPLIT_ROWS  as FTMI_FILL_ROWS, the rows holding f16x3 split rows (above): C
+ *                         heads f16(value), then C tails f16((value - h) 2^11); C % 2 == 0
+ *                         (else FTMI_E_SHAPE), 16-byte stores when C % 8 == 0.  value = 0 is
+ *                         all-zero halves.
+ * A stride below C (T for FTMI_FILL_TIME_LAST): FTMI_E_SHAPE; an unknown mode: FTMI_E_ARG.
+ *
+ * ftmi_maxpool_rows is the CBHG maxpool (MaxPool1d(2, 1, padding=1)[..., :T]) of (B, T, C)
+ * rows with such ends: y[b,t] = max(x[b,t-1], x[b,t]) (t = 0: x[b,0]) for t < len[b], zero
+ * rows from len[b] on.  C % 4 == 0, strides % 4 == 0, x / y 16-byte aligned (FTMI_E_ALIGN).
+ *
+ * ftmi_duration_counts_rows is ftmi_duration_counts decided per item: positions
+ * t >= x_len[b] get duration 0 and count 0 (x_len[b] > T counts as T); with apply_fill,
+ * row b is filled where sum_{t < x_len[b]} trunc_int64(dur[b,t]) <= 0, at its valid
+ * positions only; the clip, the count and the scan are the same arithmetic, bit for bit.
+ * fill_flags (optional int32 [B]) receives 1 for every row the rule filled.
+ * ---------------------------------------------------------------------------------- */
+enum { FTMI_FILL_ROWS = 0, FTMI_FILL_TIME_LAST = 1, FTMI_FILL_SPLIT_ROWS = 2 };
+int ftmi_fill_tail(float *x, int64_t stride, int32_t B, int32_t T, int32_t C,
+                   const int32_t *len, int32_t reach, float value, int32_t mode,
+                   ftmi_stream_t stream);
+int ftmi_maxpool_rows(const float *x, int64_t x_stride, int32_t B, int32_t T, int32_t C,
+                      const int32_t *len, float *y, int64_t y_stride, ftmi_stream_t stream);
+int ftmi_duration_counts_rows(float *dur, int32_t B, int32_t T, const int32_t *x_len,
+                              int32_t apply_fill, float fill_value, int32_t *offsets,
+                              int32_t *totals, int32_t *fill_flags, ftmi_stream_t stream);
 
 /* Frame -> phoneme index map of the LengthRegulator: index[b, f] = t such that
  * offsets[b,t] <= f < offsets[b,t+1], or -1 for f >= totals[b] (zero padding,
