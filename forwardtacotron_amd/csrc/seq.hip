@@ -280,8 +280,9 @@ extern "C" int ftmi_duration_counts_global(float *dur, int32_t B, int32_t T,
 
 extern "C" int ftmi_lr_index(const int32_t *offsets, int32_t B, int32_t T, int32_t T_mel,
                              int32_t *index, ftmi_stream_t stream) {
-  if (!offsets || !index || B <= 0 || T <= 0 || T_mel < 0) return FTMI_E_ARG;
-  if (T_mel == 0) return FTMI_OK;
+  if (!offsets || B <= 0 || T <= 0 || T_mel < 0) return FTMI_E_ARG;
+  if (T_mel == 0) return FTMI_OK;  // an empty (B, 0) map has no storage: index may be null
+  if (!index) return FTMI_E_ARG;
   hipLaunchKernelGGL(lr_index_kernel, dim3((T_mel + 255) / 256, B), dim3(256), 0,
                      ftmi_hs(stream), offsets, B, T, T_mel, index);
   FTMI_CHECK_LAUNCH();

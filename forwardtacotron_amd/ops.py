@@ -816,6 +816,8 @@ def duration_counts(dur: torch.Tensor, apply_fill: bool, fill_value: float = 2.0
 def duration_trunc_sum(dur: torch.Tensor) -> torch.Tensor:
     """sum_{b,t} int64(trunc(dur)) as a device int64[1] (the fill-2 rule's statistic)."""
     _dev(dur)
+    if dur.dtype != _f32 or not dur.is_contiguous() or dur.dim() != 2:
+        raise ValueError('dur must be a contiguous (B, T) fp32 tensor')
     B, T = dur.shape
     out = torch.empty(1, device=dur.device, dtype=torch.int64)
     launch('ftmi_duration_trunc_sum', f'duration_trunc_sum[B={B},T={T}]', 0, 4.0 * B * T,
@@ -957,12 +959,21 @@ def rowdot(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], alpha
 # --------------------------------------------------------------------------------------
 # FastPitch transformer (csrc/transformer.hip)
 
+def _check_pe(pe: torch.Tensor, rows: int, width: int, what: str) -> None:
+    """The kernels read pe[t, :width] for t < rows as contiguous fp32 rows of that width."""
+    if (pe.dim() != 2 or pe.dtype != _f32 or not pe.is_contiguous() or pe.size(1) != width
+            or pe.size(0) < rows):
+        raise ValueError(f'{what}: pe must be contiguous fp32 rows (>= {rows}, {width}), got '
+                         f'{pe.dtype} shape {tuple(pe.shape)} strides {pe.stride()}')
+
+
 def embedding_posenc(ids: torch.Tensor, table: torch.Tensor, pe: torch.Tensor,
                      scale: torch.Tensor) -> torch.Tensor:
     """(B, T) ids -> table[ids] + scale * pe[:T]  (B, T, dim)."""
     _dev(ids, table, pe, scale)
     B, T = ids.shape
     dim = table.size(1)
+    _check_pe(pe, T, dim, 'embedding_posenc')
     ids = ids.contiguous().to(torch.int64)
     out = torch.empty(B, T, dim, device=ids.device, dtype=_f32)
     launch('ftmi_embedding_posenc', f'embedding_posenc[n={B * T},d={dim}]', B * T * dim * 2.0,
@@ -977,6 +988,7 @@ def lr_posenc(x: torch.Tensor, index: torch.Tensor, pe: torch.Tensor, scale: tor
     _dev(x, index, pe, scale)
     B, T, C, xs = _rows(x)
     T_mel = index.size(1)
+    _check_pe(pe, T_mel, C, 'lr_posenc')
     y = torch.empty(B, T_mel, C, device=x.device, dtype=_f32)
     launch('ftmi_lr_posenc', f'lr_posenc[B={B},T_mel={T_mel},C={C}]', 2.0 * B * T_mel * C,
            4.0 * (B * T * C + B * T_mel * (2 * C + 1)),

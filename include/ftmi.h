@@ -533,7 +533,8 @@ int ftmi_duration_counts_rows(float *dur, int32_t B, int32_t T, const int32_t *x
 
 /* Frame -> phoneme index map of the LengthRegulator: index[b, f] = t such that
  * offsets[b,t] <= f < offsets[b,t+1], or -1 for f >= totals[b] (zero padding,
- * pad_sequence in common_layers.py:18).  index: int32 [B][T_mel]. */
+ * pad_sequence in common_layers.py:18).  index: int32 [B][T_mel]; T_mel = 0 launches nothing
+ * and takes a null index (an empty map has no storage). */
 int ftmi_lr_index(const int32_t *offsets, int32_t B, int32_t T, int32_t T_mel,
                   int32_t *index, ftmi_stream_t stream);
 
