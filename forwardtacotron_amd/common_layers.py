@@ -13,12 +13,41 @@ used (and tested) one layer at a time.
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
 from . import ops
+
+
+def check_device(weight: torch.Tensor, x: Optional[torch.Tensor], name: str,
+                 hint: str = 'call model.to("cuda") first (there is no CPU path)') -> None:
+    """The model (one of its weights) is on a HIP device, and the input x, if given, on the
+    same one.  name: the class, as the message calls it."""
+    if not weight.is_cuda:
+        raise RuntimeError(f'{name} runs on a HIP device only: {hint}')
+    if x is not None and x.device != weight.device:
+        raise RuntimeError(f'input on {x.device}, model on {weight.device}')
+
+
+def pad_time(x: torch.Tensor, max_len: int, value: float) -> torch.Tensor:
+    """Crop / pad the time axis of (B, C, T) to max_len with `value` (the reference's `pad`)."""
+    x = x[:, :, :max_len]
+    if x.size(2) < max_len:
+        pad = torch.full((x.size(0), x.size(1), max_len - x.size(2)), value,
+                         device=x.device, dtype=x.dtype)
+        x = torch.cat([x, pad], 2)
+    return x
+
+
+def series_proj_weights(pitch_proj: nn.Module, energy_proj: nn.Module):
+    """(w_p [C][3], b_p, w_e [C][3], b_e) of the pitch / energy Conv1d(1, C, 3) projections,
+    as ops.series_proj_add takes them."""
+    return (pitch_proj.weight.detach().reshape(-1, 3).contiguous(),
+            pitch_proj.bias.detach().contiguous(),
+            energy_proj.weight.detach().reshape(-1, 3).contiguous(),
+            energy_proj.bias.detach().contiguous())
 
 # --------------------------------------------------------------------------------------
 # packed-weight cache: rebuilt whenever a parameter / buffer changes (load_state_dict, .to)
@@ -223,6 +252,16 @@ class HighwayNetwork(Packed):
         return y.reshape(shp)
 
 
+class RNNPack(NamedTuple):
+    """BiRNN.packed_weights(): W_ih both directions [2*G*H][In], the input bias [2*G*H]
+    (LSTM: b_ih + b_hh), b_hh [2*G*H] (LSTM: None), W_hh [2][G*H][H], W_ih pre-split."""
+    w_ih: torch.Tensor
+    b_in: torch.Tensor
+    b_hh: Optional[torch.Tensor]
+    w_hh: torch.Tensor
+    w_ih_split: object
+
+
 class BiRNN(Packed):
     """1-layer bidirectional GRU (gates r,z,n) / LSTM (gates i,f,g,o), batch_first, holding
     exactly the parameters of nn.GRU / nn.LSTM (weight_ih_l0, weight_hh_l0, bias_ih_l0,
@@ -244,15 +283,14 @@ class BiRNN(Packed):
                 _uniform_(prm, b)
                 self.register_parameter(name + sfx, prm)
 
-    def _pack(self):
-        """W_ih both directions [2*G*H][In], input bias [2*G*H], b_hh [2*G*H], W_hh [2][G*H][H]."""
+    def _pack(self) -> RNNPack:
         w_ih = torch.cat([self.weight_ih_l0, self.weight_ih_l0_reverse], 0).detach().contiguous()
         b_ih = torch.cat([self.bias_ih_l0, self.bias_ih_l0_reverse], 0).detach().contiguous()
         b_hh = torch.cat([self.bias_hh_l0, self.bias_hh_l0_reverse], 0).detach().contiguous()
         w_hh = torch.stack([self.weight_hh_l0, self.weight_hh_l0_reverse], 0).detach().contiguous()
         if self.cell == 1:  # LSTM: both biases folded into the input projection
-            return w_ih, (b_ih + b_hh).contiguous(), None, w_hh, presplit(w_ih)
-        return w_ih, b_ih, b_hh, w_hh, presplit(w_ih)
+            return RNNPack(w_ih, (b_ih + b_hh).contiguous(), None, w_hh, presplit(w_ih))
+        return RNNPack(w_ih, b_ih, b_hh, w_hh, presplit(w_ih))
 
     def forward_cl(self, x: torch.Tensor, T: Optional[int] = None, index=None, lengths=None,
                    pad_value: float = 0.0) -> torch.Tensor:
@@ -262,21 +300,44 @@ class BiRNN(Packed):
 
     def project(self, x: torch.Tensor) -> torch.Tensor:
         """Input projections of both directions, x W_ih^T + b: (B, T_src, 2*G*H)."""
-        w_ih, b_in, _, _, w3 = self.packed_weights()
-        xp, _ = ops.conv1d(x, w_ih, 1, 0, bias=b_in, w_split=w3)
+        p = self.packed_weights()
+        xp, _ = ops.conv1d(x, p.w_ih, 1, 0, bias=p.b_in, w_split=p.w_ih_split)
         return xp
 
     def recur(self, xp: torch.Tensor, T: Optional[int] = None, index=None, lengths=None,
               pad_value: float = 0.0) -> torch.Tensor:
         """The recurrence over `project`'s output (frame t reads row index[b, t])."""
-        _, b_in, b_hh, w_hh, _ = self.packed_weights()
-        return ops.rnn_bidir(self.cell, xp, self.hidden, w_hh, b_hh, T=T, index=index,
-                             xp_zero=b_in if index is not None else None, lengths=lengths,
+        p = self.packed_weights()
+        return ops.rnn_bidir(self.cell, xp, self.hidden, p.w_hh, p.b_hh, T=T, index=index,
+                             xp_zero=p.b_in if index is not None else None, lengths=lengths,
                              pad_value=pad_value, spread=self.spread)
 
     def forward(self, x: torch.Tensor):
         """(B, T, In) -> ((B, T, 2H), None) like nn.GRU/LSTM(batch_first=True) without h0."""
         return self.forward_cl(x.contiguous()), None
+
+
+class CBHGPack(NamedTuple):
+    """CBHG.packed_weights(): the conv bank (weights, folded BN scale / shift, f16x3 planes,
+    the halves image) and pre_highway (weight, pre-split)."""
+    bank_w: torch.Tensor
+    scale: torch.Tensor
+    shift: torch.Tensor
+    w_pre: torch.Tensor
+    bank3: object
+    pre3: object
+    img: object
+
+
+class StackPack(NamedTuple):
+    """CBHG._stack_pack(): the operands of ops.highway_stack."""
+    pre_f: object
+    hw_f: list
+    b1s: list
+    b2s: list
+    ih_f: object
+    b_in: torch.Tensor
+    n_out: int
 
 
 class CBHG(Packed):
@@ -307,21 +368,21 @@ class CBHG(Packed):
         w_pre = self.pre_highway.weight.detach().contiguous()
         bank3 = ops.split_bank_weights(bank_w, self.K, ws[0].size(1), self.channels)
         img = ops.bank_halves_image(bank3, self.K, ws[0].size(1), self.channels)
-        return bank_w, scale, shift, w_pre, bank3, presplit(w_pre), img
+        return CBHGPack(bank_w, scale, shift, w_pre, bank3, presplit(w_pre), img)
 
     def forward_cl(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(B, T, Cin) channels-last -> (B, T, 2*channels).  lengths: (B,) int32 on the device
         — item b holds lengths[b] valid rows and its result on them is that of the item
         alone (see _after_bank); x must then be zero in the K // 2 rows past each item's end."""
-        bank_w, scale, shift, w_pre, bank3, pre3, img = self.packed_weights()
-        pooled = ops.bank_pools(x, self.K, self.channels, w_split=bank3)
+        p = self.packed_weights()
+        pooled = ops.bank_pools(x, self.K, self.channels, w_split=p.bank3)
         # pooled: the bank kernel applied the maxpool, and (split) stored its output as the
         # f16x3 split rows proj1 multiplies
         split = pooled and ops.SPLIT_ROWS
         xin = pooled and ops.SPLIT_BANK_IN  # x stays fp32 too: it is the proj2 residual
-        bank = ops.conv_bank(ops.split_rows(x) if xin else x, bank_w, self.K, self.channels,
-                             scale, shift, w_split=bank3, pool=pooled, split_out=split,
-                             x_split=xin, w_image=img)
+        bank = ops.conv_bank(ops.split_rows(x) if xin else x, p.bank_w, self.K, self.channels,
+                             p.scale, p.shift, w_split=p.bank3, pool=pooled, split_out=split,
+                             x_split=xin, w_image=p.img)
         return self._after_bank(bank, x, pooled, split, lengths)
 
     def embed_bank_table(self, embedding_weight: torch.Tensor) -> torch.Tensor:
@@ -347,12 +408,12 @@ class CBHG(Packed):
                 or w.size(1) != self.conv1d_bank[0].conv.in_channels
                 or not ops.embed_bank_ok(w.size(0), 1, self.K, self.channels)):
             return self.forward_cl(h, lengths)
-        _, scale, shift, _, bank3 = self.packed_weights()[:5]
+        p = self.packed_weights()
         # split rows exactly where forward_cl's pooled bank would store them (proj1 then reads
         # them on the f16x3 slab kernel); fp32 rows elsewhere and under ops.exact_paths()
-        split = ops.SPLIT_ROWS and ops.bank_pools(h, self.K, self.channels, w_split=bank3)
-        bank = ops.embed_bank(x_ids, self.embed_bank_table(w), 1, self.K, self.channels, scale,
-                              shift, pool=True, split_out=split)
+        split = ops.SPLIT_ROWS and ops.bank_pools(h, self.K, self.channels, w_split=p.bank3)
+        bank = ops.embed_bank(x_ids, self.embed_bank_table(w), 1, self.K, self.channels, p.scale,
+                              p.shift, pool=True, split_out=split)
         return self._after_bank(bank, h, True, split, lengths)
 
     def _after_bank(self, bank: torch.Tensor, x: torch.Tensor, pooled: bool,
@@ -366,7 +427,6 @@ class CBHG(Packed):
         ops.maxpool_rows, which also writes the zero rows, since no row of the unpooled
         bank can make max(bank[L-1], bank[L]) zero).  The layers after proj2 are pointwise,
         and the GRU takes the lengths (pack_padded_sequence semantics)."""
-        bank_w, scale, shift, w_pre, bank3, pre3, img = self.packed_weights()
         if lengths is not None:
             if pooled:
                 ops.fill_tail(bank, lengths, reach=1, split=bool(split))
@@ -380,7 +440,8 @@ class CBHG(Packed):
         xp = self._highway_stack(y)
         if xp is not None:
             return self.rnn.recur(xp, lengths=lengths)
-        h, _ = ops.conv1d(y, w_pre, 1, 0, w_split=pre3)
+        p = self.packed_weights()
+        h, _ = ops.conv1d(y, p.w_pre, 1, 0, w_split=p.pre3)
         h2 = torch.empty_like(h)
         for hw in self.highways:
             hw.forward_cl(h, out=h2)
@@ -391,13 +452,13 @@ class CBHG(Packed):
         """Fragment-major f16x3 blocks of pre_highway, the highways' w12 and the GRU's W_ih
         (the operands of ops.highway_stack), cached like every pack (rebuilt with the params)."""
         def build():
-            w_pre = self.packed_weights()[3]
             hw = [m.packed_weights() for m in self.highways]
-            w_ih, b_in = self.rnn.packed_weights()[:2]
+            rnn = self.rnn.packed_weights()
             f16 = ops.split_weights_f16
-            return (f16(w_pre, frag=True), [f16(p[0], frag=True) for p in hw],
-                    [p[1] for p in hw], [p[2] for p in hw], f16(w_ih, frag=True), b_in,
-                    w_ih.size(0))
+            return StackPack(f16(self.packed_weights().w_pre, frag=True),
+                             [f16(p[0], frag=True) for p in hw], [p[1] for p in hw],
+                             [p[2] for p in hw], f16(rnn.w_ih, frag=True), rnn.b_in,
+                             rnn.w_ih.size(0))
         return cached_pack(self, '_ftmi_stack', build)
 
     def spread_blocks(self, M: int) -> int:
@@ -405,7 +466,7 @@ class CBHG(Packed):
         stack does not apply or runs the one-workgroup-per-64-rows kernel)."""
         Cp = self.channels  # the tail's input: proj2's output (common_layers.py:104-109)
         if not ops.highway_stack_ok(M, Cp, self.channels, len(self.highways), 6 * self.channels,
-                                    (self.packed_weights()[5],)):
+                                    (self.packed_weights().pre3,)):
             return 0
         return ops.hs_spread_blocks(M, 6 * self.channels)
 
@@ -416,11 +477,11 @@ class CBHG(Packed):
         M, Cp = y.size(0) * y.size(1), y.size(2)
         n_out = 6 * self.channels
         if not ops.highway_stack_ok(M, Cp, self.channels, len(self.highways), n_out,
-                                    (self.packed_weights()[5],)):
+                                    (self.packed_weights().pre3,)):
             return None
-        pre_f, hw_f, b1s, b2s, ih_f, b_in, n_out = self._stack_pack()
-        xp, _ = ops.highway_stack(y, pre_f, self.channels, hw_f, b1s, b2s, ih_f, b_in, n_out,
-                                  spread=getattr(self, 'allow_spread', True))
+        s = self._stack_pack()
+        xp, _ = ops.highway_stack(y, s.pre_f, self.channels, s.hw_f, s.b1s, s.b2s, s.ih_f,
+                                  s.b_in, s.n_out, spread=getattr(self, 'allow_spread', True))
         return xp
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -25,7 +25,7 @@ import torch.nn as nn
 
 from . import ops, phase_graph
 from .common_layers import (Conv1dParams, LengthRegulator, LinearParams, Packed, cached_pack,
-                            pack_conv, presplit)
+                            check_device, pack_conv, pad_time, presplit, series_proj_weights)
 from .forward_tacotron import Embedding
 from .phase_graph import _identity
 from .text.symbols import phonemes
@@ -263,25 +263,19 @@ class FastPitch(nn.Module):
 
     # ---------------------------------------------------------------------------------
     def _check_device(self, x: torch.Tensor) -> None:
-        if not self.embedding.weight.is_cuda:
-            raise RuntimeError('forwardtacotron_amd.FastPitch runs on a HIP device only: call '
-                               'model.to("cuda") first (there is no CPU path)')
-        if x.device != self.embedding.weight.device:
-            raise RuntimeError(f'input on {x.device}, model on {self.embedding.weight.device}')
+        check_device(self.embedding.weight, x, 'forwardtacotron_amd.FastPitch')
 
-    def _series_proj_weights(self):
-        return (self.pitch_proj.weight.detach().reshape(-1, 3).contiguous(),
-                self.pitch_proj.bias.detach().contiguous(),
-                self.energy_proj.weight.detach().reshape(-1, 3).contiguous(),
-                self.energy_proj.bias.detach().contiguous())
+    def _add_series(self, h, pitch, energy) -> None:
+        """h += pitch_strength proj_p(pitch) + energy_strength proj_e(energy), in place."""
+        wp, bp, we, be = series_proj_weights(self.pitch_proj, self.energy_proj)
+        ops.series_proj_add(h, pitch, wp, bp, self.pitch_strength, energy, we, be,
+                            self.energy_strength)
 
     def _encode(self, x, pitch, energy, len_mask):
         """embedding + prenet (key_padding_mask = x == 0) + pitch / energy projections."""
         h = self.prenet.embed(x, self.embedding.weight.detach())
         h = self.prenet.layers_cl(h, len_mask)
-        wp, bp, we, be = self._series_proj_weights()
-        ops.series_proj_add(h, pitch, wp, bp, self.pitch_strength, energy, we, be,
-                            self.energy_strength)
+        self._add_series(h, pitch, energy)
         return h
 
     def _decode(self, enc, index, kpm=None):
@@ -329,11 +323,11 @@ class FastPitch(nn.Module):
     def _phase(self, x, alpha, pitch_function, energy_function, batch=None, capture=False):
         """The phoneme phase: the prenet on a side stream beside the pitch / energy
         predictors, the duration predictor and counts on the caller's stream, then the
-        pitch / energy projections added to the prenet output.  Returns (dur_hat, pitch_hat,
-        energy_hat, h, offsets, T_mel); capture=True (graph capture): no host sync, the T_mel
-        slot holds max(totals) on the device.  pitch_function = energy_function = None
-        (capture only): the predictors' raw outputs, h without their projections (the split
-        graph of _phase_graph)."""
+        pitch / energy projections added to the prenet output h.  Returns a phase_graph.Phase
+        (no index map yet); capture=True (graph capture): no host sync, t_mel holds
+        max(totals) on the device.  pitch_function = energy_function = None (capture only):
+        the predictors' raw outputs, h without their projections (the split graph of
+        phase_graph)."""
         main = torch.cuda.current_stream(x.device)
         s_pitch, s_energy, s_prenet = self._side_streams(x.device)
         for s in (s_pitch, s_energy, s_prenet):
@@ -363,50 +357,21 @@ class FastPitch(nn.Module):
             if not capture:
                 t.record_stream(main)
         if pitch_function is not None and energy_function is not None:
-            wp, bp, we, be = self._series_proj_weights()
-            ops.series_proj_add(h, pitch_hat, wp, bp, self.pitch_strength, energy_hat, we, be,
-                                self.energy_strength)
-        return dur_hat, pitch_hat, energy_hat, h, offsets, T_mel
-
-    def _phase_graph(self, x, alpha, pitch_fn, energy_fn):
-        """The phoneme phase from its HIP graph (phase_graph.replay), keyed with the GEMM
-        matrix path.  The split graph leaves h without the pitch / energy projections: they
-        are added eagerly.  Returns ((dur, pitch, energy, h, offsets, T_mel), entry) or None
-        (run the eager phase)."""
-        def finish(phase):
-            wp, bp, we, be = self._series_proj_weights()
-            ops.series_proj_add(phase[3], phase[1], wp, bp, self.pitch_strength, phase[2], we,
-                                be, self.energy_strength)
-        return phase_graph.replay(
-            self, x, alpha, pitch_fn, energy_fn, (ops.MMA,),
-            lambda sx, p, e: self._phase(sx, alpha, p, e, capture=True), finish)
+            self._add_series(h, pitch_hat, energy_hat)
+        return phase_graph.Phase(dur_hat, pitch_hat, energy_hat, h, offsets, T_mel)
 
     def _generate(self, x, alpha, pitch_function, energy_function, batch):
+        """Phoneme phase (from its HIP graph, keyed with the GEMM matrix path, where one may be
+        used; a split graph's finish adds the projections eagerly) -> decoder."""
         with torch.no_grad():
-            phase = ent = None
-            if FP_GRAPH and batch is None and not ops.forced_exact():
-                r = self._phase_graph(x, alpha, pitch_function, energy_function)
-                if r is not None:
-                    phase, ent = r
-            if phase is None:
-                phase = self._phase(x, alpha, pitch_function, energy_function, batch)
-            dur_hat, pitch_hat, energy_hat, h, offsets, T_mel = phase
-            index = ops.lr_index(offsets, T_mel)
-            mel = self._decode(h, index)
-            if ent is not None:  # the decoder has consumed the graph's static buffers
-                ent['done'].record(torch.cuda.current_stream(x.device))
-            return {'mel': mel, 'mel_post': mel, 'dur': dur_hat,
-                    'pitch': pitch_hat, 'energy': energy_hat}
-
-    def _generate_mel(self, x, dur_hat, pitch_hat, energy_hat):
-        """`models/fast_pitch.py:315-340`."""
-        with torch.no_grad():
-            h = self._encode(x, pitch_hat, energy_hat, x == 0)
-            offsets, totals, _ = ops.duration_counts(dur_hat, apply_fill=False)
-            T_mel = int(totals.max().item())
-            mel = self._decode(h, ops.lr_index(offsets, T_mel))
-        return {'mel': mel, 'mel_post': mel, 'dur': dur_hat, 'pitch': pitch_hat,
-                'energy': energy_hat}
+            phase, consumed = phase_graph.phoneme_phase(
+                self, self._phase, lambda ph: self._add_series(ph.h, ph.pitch, ph.energy),
+                (ops.MMA,), x, alpha, pitch_function, energy_function, batch,
+                FP_GRAPH and not ops.forced_exact())
+            mel = self._decode(phase.h, ops.lr_index(phase.offsets, phase.t_mel))
+            consumed()  # the decoder is queued: the graph's static buffers may be rewritten
+            return {'mel': mel, 'mel_post': mel, 'dur': phase.dur,
+                    'pitch': phase.pitch, 'energy': phase.energy}
 
     def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """Teacher-forced pass (`models/fast_pitch.py:233-283`), inference numerics."""
@@ -445,12 +410,7 @@ class FastPitch(nn.Module):
 
     def pad(self, x: torch.Tensor, max_len: int) -> torch.Tensor:
         """`models/fast_pitch.py:305-308`."""
-        x = x[:, :, :max_len]
-        if x.size(2) < max_len:
-            pad = torch.full((x.size(0), x.size(1), max_len - x.size(2)), self.padding_value,
-                             device=x.device, dtype=x.dtype)
-            x = torch.cat([x, pad], 2)
-        return x
+        return pad_time(x, max_len, self.padding_value)
 
     def get_step(self) -> int:
         return self.step.data.item()

@@ -29,7 +29,8 @@ import torch.nn as nn
 
 from . import _lib, chain, ops, phase_graph
 from .common_layers import (CBHG, BatchNormConv, BiRNN, Conv1dParams, LengthRegulator,
-                            LinearParams, Packed, cached_pack, pack_conv)
+                            LinearParams, Packed, cached_pack, check_device, pack_conv, pad_time,
+                            series_proj_weights)
 from .phase_graph import _graphable, _identity, graph_safe  # noqa: F401  (public here)
 from .text.symbols import phonemes
 
@@ -206,18 +207,8 @@ class ForwardTacotron(nn.Module):
         return f'ForwardTacotron, num params: {num_params}'
 
     # ---------------------------------------------------------------------------------
-    def _check_device(self, x: torch.Tensor) -> None:
-        if not self.embedding.weight.is_cuda:
-            raise RuntimeError('forwardtacotron_amd.ForwardTacotron runs on a HIP device only: '
-                               'call model.to("cuda") first (there is no CPU path)')
-        if x.device != self.embedding.weight.device:
-            raise RuntimeError(f'input on {x.device}, model on {self.embedding.weight.device}')
-
-    def _series_proj_weights(self):
-        return (self.pitch_proj.weight.detach().reshape(-1, 3).contiguous(),
-                self.pitch_proj.bias.detach().contiguous(),
-                self.energy_proj.weight.detach().reshape(-1, 3).contiguous(),
-                self.energy_proj.bias.detach().contiguous())
+    def _check_device(self, x=None) -> None:
+        check_device(self.embedding.weight, x, 'forwardtacotron_amd.ForwardTacotron')
 
     def _folded_series_weights(self):
         """The pitch / energy projections carried through the LSTM's input projection:
@@ -229,7 +220,7 @@ class ForwardTacotron(nn.Module):
         pp, ep = self.pitch_proj, self.energy_proj
 
         def build():
-            w_ih = self.lstm.packed_weights()[0].double()  # [2*4H][In], both directions
+            w_ih = self.lstm.packed_weights().w_ih.double()  # [2*4H][In], both directions
             out = []
             for w, b in (pp.weight, pp.bias), (ep.weight, ep.bias):
                 out.append((w_ih @ w.detach().double().reshape(-1, 3)).float().contiguous())
@@ -239,34 +230,47 @@ class ForwardTacotron(nn.Module):
             pp.weight._version, pp.bias._version, ep.weight._version, ep.bias._version,
             pp.weight.data_ptr(), ep.weight.data_ptr()))
 
+    def _add_series(self, h, pitch, energy, folded=True) -> None:
+        """h += pitch_strength proj_p(pitch) + energy_strength proj_e(energy), in place.
+        folded: h holds LSTM input projection rows (_folded_series_weights), not prenet rows."""
+        wp, bp, we, be = (self._folded_series_weights() if folded
+                          else series_proj_weights(self.pitch_proj, self.energy_proj))
+        ops.series_proj_add(h, pitch, wp, bp, self.pitch_strength, energy, we, be,
+                            self.energy_strength)
+
     def _encode(self, x: torch.Tensor, pitch: torch.Tensor, energy: torch.Tensor) -> torch.Tensor:
         """embedding -> prenet CBHG -> + pitch / energy projections: (B, T, 2*prenet_dims)."""
         h = ops.embedding(x, self.embedding.weight.detach())
         h = self.prenet.forward_cl(h)
-        wp, bp, we, be = self._series_proj_weights()
-        ops.series_proj_add(h, pitch, wp, bp, self.pitch_strength, energy, we, be,
-                            self.energy_strength)
+        self._add_series(h, pitch, energy, folded=False)
         return h
 
-    def _decode(self, enc: torch.Tensor, index: torch.Tensor, lengths=None, T_out=None, xp=None):
-        """LSTM over LR(enc) (through the index map) -> lin -> postnet -> post_proj.
-        xp: the LSTM input projection of enc if already queued (self.lstm.project)."""
-        B = enc.size(0)
-        T_mel = index.size(1)
-        if xp is None:
-            xp = self.lstm.project(enc)
+    def _decode(self, xp: torch.Tensor, index: torch.Tensor, *, lengths=None, pad_value=None,
+                item_frames=None):
+        """The decoder tail on xp, the LSTM input projection at phoneme rate: the LSTM reads
+        it through the LR index map -> lin -> postnet -> post_proj.  lengths / pad_value
+        (default padding_value): the recurrence's.  item_frames: the per-item frame totals
+        of a length-aware batch ((B,) int32 on the device): the rows past an item's end are
+        filled where a conv would read them or the caller sees them (ops.fill_tail) and the
+        postnet takes the lengths; None: exactly the launches without them."""
+        B, T_mel, dev = xp.size(0), index.size(1), xp.device
         lstm_out = self.lstm.recur(xp, T=T_mel, index=index, lengths=lengths,
-                                   pad_value=self.padding_value)
+                                   pad_value=self.padding_value if pad_value is None else pad_value)
         del xp
-        mel_cl = torch.empty(B, T_mel, self.n_mels, device=enc.device)
-        mel = torch.empty(B, self.n_mels, T_mel, device=enc.device)
+        mel_cl = torch.empty(B, T_mel, self.n_mels, device=dev)
+        mel = torch.empty(B, self.n_mels, T_mel, device=dev)
         w, b, w3 = self.lin.packed_weights()
         ops.conv1d(lstm_out, w, 1, 0, bias=b, out=mel_cl, out_t=mel, w_split=w3)
         del lstm_out
-        post = self.postnet.forward_cl(mel_cl)
-        mel_post = torch.empty(B, self.n_mels, T_mel, device=enc.device)
+        if item_frames is not None:  # mel_cl: the postnet bank's input and residual
+            ops.fill_tail(mel_cl, item_frames, reach=self.postnet.K // 2)
+            ops.fill_tail(mel, item_frames, value=self.padding_value, time_last=True)
+        post = self.postnet.forward_cl(mel_cl, lengths=item_frames)
+        mel_post = torch.empty(B, self.n_mels, T_mel, device=dev)
         w, _, w3 = self.post_proj.packed_weights()
         ops.conv1d(post, w, 1, 0, out_t=mel_post, want_y=False, w_split=w3)
+        if item_frames is not None:
+            ops.fill_tail(mel_post, item_frames, value=self.padding_value, time_last=True)
         return mel, mel_post
 
     # ---------------------------------------------------------------------------------
@@ -299,7 +303,8 @@ class ForwardTacotron(nn.Module):
             if T_pack > int(totals.max().item()):
                 raise RuntimeError('mel_len exceeds the length-regulated sequence length')
             index = ops.lr_index(offsets, T_pack)
-            x_mel, x_post = self._decode(enc, index, lengths=lens.to(x.device))
+            lens = lens.to(x.device)
+            x_mel, x_post = self._decode(self.lstm.project(enc), index, lengths=lens)
             x_post = self._pad(x_post, mel.size(2))
             x_mel = self._pad(x_mel, mel.size(2))
         return {'mel': x_mel, 'mel_post': x_post,
@@ -346,19 +351,6 @@ class ForwardTacotron(nn.Module):
             return [main, main, main]
         return cache[device]
 
-    def _phoneme_graph(self, x, alpha, pitch_fn, energy_fn):
-        """The phoneme phase (unsharded) from its HIP graph (phase_graph.replay: ~40 launches
-        from Python become one replay), keyed with both matrix paths.  The split graph
-        leaves xp without the pitch / energy terms: they are added eagerly, folded through
-        W_ih.  Returns (phase outputs, entry) or None (run the eager phase)."""
-        def finish(phase):
-            wp, bp, we, be = self._folded_series_weights()
-            ops.series_proj_add(phase[6], phase[1], wp, bp, self.pitch_strength, phase[2], we,
-                                be, self.energy_strength)
-        return phase_graph.replay(
-            self, x, alpha, pitch_fn, energy_fn, (ops.MMA, ops.RNN_MMA),
-            lambda sx, p, e: self._phoneme_phase(sx, alpha, p, e, capture=True), finish)
-
     def _phoneme_phase(self, x, alpha, pitch_fn, energy_fn, batch=None, capture=False):
         """Duration / pitch / energy predictors and the prenet CBHG are independent: pitch,
         energy and the prenet run on three side streams while the caller's stream runs the
@@ -369,14 +361,14 @@ class ForwardTacotron(nn.Module):
         none of it depends on T_mel, so it runs while the duration path finishes and the
         host waits for T_mel (the one host sync, a pinned copy queued right after the
         duration kernel).  Issue order = priority order: prenet, durations, pitch,
-        energy.  Returns (dur_hat, pitch_hat, energy_hat, enc, (offsets, index), T_mel, xp)
-        with every tensor ready on the caller's stream (xp: the LSTM input projection of enc
-        plus the pitch / energy projections, folded through W_ih; enc itself does not carry
-        them; index: the LR index map, queued on the caller's stream before it joins the side
-        streams).  capture=True (graph capture, see phase_graph): no host sync, the T_mel
-        slot holds max(totals) on the device and the offsets slot plain offsets.
+        energy.  Returns a phase_graph.Phase with every tensor ready on the caller's stream
+        (h: the LSTM input projection of the prenet output plus the pitch / energy
+        projections, folded through W_ih; the prenet output itself is last read on the
+        prenet stream and freed there; index: the LR index map, queued on the caller's
+        stream before it joins the side streams).  capture=True (graph capture, see
+        phase_graph): no host sync, t_mel holds max(totals) on the device and index None.
         pitch_fn = energy_fn = None (capture only): the predictors' raw outputs are returned
-        and xp does not carry their projections yet (the split graph of phase_graph)."""
+        and h does not carry their projections yet (the split graph of phase_graph)."""
         main = torch.cuda.current_stream(x.device)
         s_pitch, s_energy, s_prenet = self._side_streams(x.device, x.size(0), x.size(1))
         for s in (s_pitch, s_energy, s_prenet):
@@ -388,18 +380,16 @@ class ForwardTacotron(nn.Module):
             xp = self.lstm.project(enc)
         dur_hat = self.dur_pred.forward_bt(x, alpha=alpha)
         t_host = t_ready = None
-        tmax = None
-        if batch is None and capture:
+        if batch is None:
             offsets, totals, _ = ops.duration_counts(dur_hat, apply_fill=True)
-            tmax = totals.max()
-        elif batch is None:
-            offsets, totals, _ = ops.duration_counts(dur_hat, apply_fill=True)
-            # the one host sync (output size is data dependent): max(totals) goes to pinned
-            # host memory now and is read after the T_mel-independent work is queued
-            t_host = torch.empty((), dtype=totals.dtype, pin_memory=True)
-            t_host.copy_(totals.max(), non_blocking=True)
-            t_ready = torch.cuda.Event()
-            t_ready.record(main)
+            T_mel = totals.max()
+            if not capture:
+                # the one host sync (output size is data dependent): max(totals) goes to pinned
+                # host memory now and is read after the T_mel-independent work is queued
+                t_host = torch.empty((), dtype=totals.dtype, pin_memory=True)
+                t_host.copy_(T_mel, non_blocking=True)
+                t_ready = torch.cuda.Event()
+                t_ready.record(main)
         with torch.cuda.stream(s_pitch):
             pitch_hat = self.pitch_pred.forward_bt(x).unsqueeze(1)
             if pitch_fn is not None:
@@ -414,9 +404,7 @@ class ForwardTacotron(nn.Module):
                     s_prenet.wait_stream(s)
                     if not capture:
                         t.record_stream(s_prenet)
-                wp, bp, we, be = self._folded_series_weights()
-                ops.series_proj_add(xp, pitch_hat, wp, bp, self.pitch_strength, energy_hat, we,
-                                    be, self.energy_strength)
+                self._add_series(xp, pitch_hat, energy_hat)
         if batch is not None:  # a shard of a larger batch (sharded.GlobalBatch): batch-global
             offsets, totals = batch.duration_counts(dur_hat)  # fill rule / T_mel
             T_mel = batch.t_mel(totals)
@@ -428,15 +416,31 @@ class ForwardTacotron(nn.Module):
             # the LR index map only needs the durations: queued before the caller's stream
             # joins the side streams, so it is not held behind the prenet chain's tail
             index = ops.lr_index(offsets, T_mel)
-        for s, ts in ((s_pitch, (pitch_hat,)), (s_energy, (energy_hat,)),
-                      (s_prenet, (enc, xp))):
+        for s, t in ((s_pitch, pitch_hat), (s_energy, energy_hat), (s_prenet, xp)):
             main.wait_stream(s)
             if not capture:
-                for t in ts:
-                    t.record_stream(main)
-        if capture:
-            return dur_hat, pitch_hat, energy_hat, enc, offsets, tmax, xp
-        return dur_hat, pitch_hat, energy_hat, enc, (offsets, index), T_mel, xp
+                t.record_stream(main)
+        return phase_graph.Phase(dur_hat, pitch_hat, energy_hat, xp, offsets, T_mel, index)
+
+    def _generate(self, x, alpha, pitch_fn, energy_fn, batch=None, graph=False):
+        """The run body of generate / generate_jit under the f16x3 range guard: phoneme phase
+        (from its graph where `graph` says so) -> decoder tail -> the reference's dictionary."""
+        def finish(ph):  # what a split graph leaves out: the projections, folded through W_ih
+            self._add_series(ph.h, ph.pitch, ph.energy)
+
+        def run():
+            with torch.no_grad():
+                phase, consumed = phase_graph.phoneme_phase(
+                    self, self._phoneme_phase, finish, (ops.MMA, ops.RNN_MMA), x, alpha,
+                    pitch_fn, energy_fn, batch, graph and not ops.forced_exact())
+                index = phase.index
+                if index is None:  # a replayed phase: T_mel was not known inside the graph
+                    index = ops.lr_index(phase.offsets, phase.t_mel)
+                mel, mel_post = self._decode(phase.h, index)
+                consumed()  # the decoder is queued: the graph's static buffers may be rewritten
+                return {'mel': mel, 'mel_post': mel_post, 'dur': phase.dur,
+                        'pitch': phase.pitch, 'energy': phase.energy}
+        return ops.run_checked(run, x.device, reduce=None if batch is None else batch.status)
 
     def generate(self,
                  x: torch.Tensor,
@@ -456,23 +460,7 @@ class ForwardTacotron(nn.Module):
         # Python-side state an arbitrary callback reads; any other callback runs eagerly
         # between the captured predictors and the launch that consumes its output
         graph = GRAPH and batch is None and x.numel() <= GRAPH_MAX_TOKENS
-
-        def run():
-            with torch.no_grad():
-                phase = ent = None
-                if graph and not ops.forced_exact():
-                    r = self._phoneme_graph(x, alpha, pitch_function, energy_function)
-                    if r is not None:
-                        phase, ent = r
-                if phase is None:
-                    phase = self._phoneme_phase(x, alpha, pitch_function, energy_function, batch)
-                dur_hat, pitch_hat, energy_hat, enc, offsets, T_mel, xp = phase
-                out = self._generate_mel(x, dur_hat, pitch_hat, energy_hat, enc=enc,
-                                         lr=(offsets, T_mel), xp=xp)
-                if ent is not None:  # the decoder has consumed the graph's static buffers
-                    ent['done'].record(torch.cuda.current_stream(x.device))
-                return out
-        return ops.run_checked(run, x.device, reduce=None if batch is None else batch.status)
+        return self._generate(x, alpha, pitch_function, energy_function, batch, graph)
 
     # ---------------------------------------------------------------------------------
     # length-aware batches: each item's result is that of generate() on the item alone
@@ -506,29 +494,13 @@ class ForwardTacotron(nn.Module):
         enc = self.prenet.forward_ids(ids, self.embedding.weight, lengths=lens)
         xp = self.lstm.project(enc)
         del enc
-        wp, bp, we, be = self._folded_series_weights()
-        ops.series_proj_add(xp, pitch, wp, bp, self.pitch_strength, energy, we, be,
-                            self.energy_strength)
+        self._add_series(xp, pitch, energy)
         t_ready.synchronize()
         tot = t_host.clone()
-        T_mel = int(tot.max())
-        index = ops.lr_index(offsets, T_mel)
+        index = ops.lr_index(offsets, int(tot.max()))
         # the decoder of forward(): frames past an item's total are skipped by the LSTM (zero
         # rows, so lin leaves its bias there, not lin(padding_value))
-        lstm_out = self.lstm.recur(xp, T=T_mel, index=index, lengths=totals, pad_value=0.0)
-        del xp
-        mel_cl = torch.empty(B, T_mel, self.n_mels, device=dev)
-        mel = torch.empty(B, self.n_mels, T_mel, device=dev)
-        w, b, w3 = self.lin.packed_weights()
-        ops.conv1d(lstm_out, w, 1, 0, bias=b, out=mel_cl, out_t=mel, w_split=w3)
-        del lstm_out
-        ops.fill_tail(mel_cl, totals, reach=self.postnet.K // 2)  # the bank's input and residual
-        ops.fill_tail(mel, totals, value=self.padding_value, time_last=True)
-        post = self.postnet.forward_cl(mel_cl, lengths=totals)
-        mel_post = torch.empty(B, self.n_mels, T_mel, device=dev)
-        w, _, w3 = self.post_proj.packed_weights()
-        ops.conv1d(post, w, 1, 0, out_t=mel_post, want_y=False, w_split=w3)
-        ops.fill_tail(mel_post, totals, value=self.padding_value, time_last=True)
+        mel, mel_post = self._decode(xp, index, lengths=totals, pad_value=0.0, item_frames=totals)
         return {'mel': mel, 'mel_post': mel_post, 'dur': dur, 'pitch': pitch,
                 'energy': energy, 'mel_len': tot.to(torch.int64)}, tot
 
@@ -609,10 +581,8 @@ class ForwardTacotron(nn.Module):
                 raise ValueError(f'xs[{i}]: integer token ids expected, got {a.dtype}')
             seqs.append(a.astype(np.int64))
         chunks, inverse = batch_plan([a.size for a in seqs], max_batch)
+        self._check_device()
         dev = self.embedding.weight.device
-        if not self.embedding.weight.is_cuda:
-            raise RuntimeError('forwardtacotron_amd.ForwardTacotron runs on a HIP device only: '
-                               'call model.to("cuda") first (there is no CPU path)')
         flat = []
         for chunk in chunks:
             lens = [seqs[i].size for i in chunk]
@@ -645,51 +615,14 @@ class ForwardTacotron(nn.Module):
     def generate_jit(self, x: torch.Tensor, alpha: float = 1.0, beta: float = 1.0) -> Dict[str, torch.Tensor]:
         """`models/forward_tacotron.py:270-284` (pitch scaled by beta, no callbacks)."""
         self._check_device(x)
-
-        def run():
-            with torch.no_grad():
-                dur_hat, pitch_hat, energy_hat, enc, offsets, T_mel, xp = self._phoneme_phase(
-                    x, alpha, lambda p: p * beta, lambda e: e)
-                return self._generate_mel(x, dur_hat, pitch_hat, energy_hat, enc=enc,
-                                          lr=(offsets, T_mel), xp=xp)
-        return ops.run_checked(run, x.device)
+        return self._generate(x, alpha, lambda p: p * beta, lambda e: e)
 
     def get_step(self) -> int:
         return self.step.data.item()
 
-    def _generate_mel(self, x, dur_hat, pitch_hat, energy_hat, enc=None, lr=None, xp=None):
-        """`models/forward_tacotron.py:289-330`.  enc: the prenet output if already computed;
-        lr: (offsets, T_mel) if the LengthRegulator counts were already computed (then
-        dur_hat has already been clipped / filled in place); xp: the LSTM input projection
-        with the pitch / energy terms if already queued (then enc is not read)."""
-        if enc is None:
-            enc = self.prenet.forward_ids(x, self.embedding.weight)
-        if xp is None:
-            wp, bp, we, be = self._series_proj_weights()
-            ops.series_proj_add(enc, pitch_hat, wp, bp, self.pitch_strength, energy_hat, we, be,
-                                self.energy_strength)
-        index = None
-        if lr is None:
-            offsets, totals, _ = ops.duration_counts(dur_hat, apply_fill=False)
-            T_mel = int(totals.max().item())  # the one host sync: output size is data dependent
-        else:
-            offsets, T_mel = lr
-            if isinstance(offsets, tuple):  # (offsets, index map already queued)
-                offsets, index = offsets
-        if index is None:
-            index = ops.lr_index(offsets, T_mel)
-        mel, mel_post = self._decode(enc, index, xp=xp)
-        return {'mel': mel, 'mel_post': mel_post, 'dur': dur_hat,
-                'pitch': pitch_hat, 'energy': energy_hat}
-
     def _pad(self, x: torch.Tensor, max_len: int) -> torch.Tensor:
         """`models/forward_tacotron.py:332-335` (crop / pad the time axis with padding_value)."""
-        x = x[:, :, :max_len]
-        if x.size(2) < max_len:
-            pad = torch.full((x.size(0), x.size(1), max_len - x.size(2)), self.padding_value,
-                             device=x.device, dtype=x.dtype)
-            x = torch.cat([x, pad], 2)
-        return x
+        return pad_time(x, max_len, self.padding_value)
 
     @classmethod
     def from_config(cls, config: Dict[str, Any]) -> 'ForwardTacotron':

@@ -3,8 +3,10 @@
 A model's phoneme phase (predictors, prenet, duration counts) is tens to hundreds of
 launches from Python over four streams; as a graph it is one replay, which matters where
 the kernels are short (batch 1: the host issue rate, not the device, sets the phase's
-length).  `replay` holds what ForwardTacotron and FastPitch share; a model brings its key
-part, its capture function and the eager finish of a split graph.
+length).  Both models' phases return one record, `Phase`; `phoneme_phase` is the way into
+either (the graph where it may be used, else the eager phase) and `replay` holds what the
+graphs share; a model brings its phase function, its key part (`policy`) and the eager
+finish of a split graph.
 
 Keyed on (device, x shape, alpha, the callbacks' identity, the model's `policy`: its matrix
 paths); a key is captured the SECOND time it is seen (a one-off shape — gen_forward.py's
@@ -22,9 +24,10 @@ launch.  The split graph is keyed 'split', without the callbacks' identity (they
 in it).
 
 Static buffers: x is copied in, dur / pitch / energy are cloned out (they go back to the
-caller); everything else in the phase tuple is consumed by this call's decoder — the next
-replay waits for the decoder's completion event (generate() records entry['done']), so
-calls on different streams never overwrite buffers a decoder still reads.
+caller); h and offsets are consumed by this call's decoder — the next replay waits for the
+decoder's completion event (entry['done'], recorded by the `consumed` callable that
+`phoneme_phase` hands out with the record), so calls on different streams never overwrite
+buffers a decoder still reads.
 
 An entry keeps every weight pack of the model alive (common_layers.held_packs: the
 captured kernels point into them) and the model-wide weights key of its capture: after
@@ -35,14 +38,25 @@ outputs are discarded).
 """
 from __future__ import annotations
 
-from typing import Callable
+from typing import Callable, NamedTuple, Optional, Union
 
 import torch
 
 from .common_layers import held_packs, weights_key
 
 CACHE = 8  # captured phases kept per model (least recently used dropped)
-TMAX = 5   # a phase tuple is (dur, pitch, energy, ..., T_mel at TMAX, ...)
+
+
+class Phase(NamedTuple):
+    """What a model's phoneme phase hands to its decoder.  dur (B, T), pitch and energy
+    (B, 1, T) go back to the caller: replay clones them out of the static buffers."""
+    dur: torch.Tensor
+    pitch: torch.Tensor
+    energy: torch.Tensor
+    h: torch.Tensor  # the rows the decoder reads; a split graph's finish adds into them
+    offsets: torch.Tensor  # the LengthRegulator offsets of ops.duration_counts
+    t_mel: Union[int, torch.Tensor]  # max(totals): on the device while captured, else an int
+    index: Optional[torch.Tensor] = None  # the LR index map where the phase queued it already
 
 
 def _identity(t: torch.Tensor) -> torch.Tensor:
@@ -65,14 +79,14 @@ def _graphable(fn) -> bool:
     return fn is _identity or getattr(fn, '_ftmi_graph_safe', False) is True
 
 
-def replay(model, x, alpha, pitch_fn, energy_fn, policy, capture, finish):
+def replay(model, phase_fn, finish, policy, x, alpha, pitch_fn, energy_fn):
     """One phoneme phase of `model` from its captured graph (see the module docstring).
-    capture(sx, pitch_fn, energy_fn): the model's phase on the static input sx without a
-    host sync, returning the eager phase's tuple with max(totals) on the device at TMAX
-    (pitch_fn = energy_fn = None: the split graph — raw predictor outputs, their
-    projections not added).  finish(phase): the launch a split graph leaves out, on the
-    phase tuple that holds the callbacks' results.  Returns (phase tuple with T_mel read to
-    the host, entry) or None (run the eager phase)."""
+    phase_fn(sx, alpha, pitch_fn, energy_fn, capture=True): the model's phase on the static
+    input sx without a host sync, returning a Phase with t_mel on the device (pitch_fn =
+    energy_fn = None: the split graph — raw predictor outputs, their projections not added
+    to h).  finish(phase): the launch a split graph leaves out, on the Phase that holds the
+    callbacks' results.  policy: the model's part of the key.  Returns (Phase with t_mel
+    read to the host, entry) or None (run the eager phase)."""
     cache = model.__dict__.setdefault('_ftmi_graphs', {})
     seen = model.__dict__.setdefault('_ftmi_graph_seen', {})
     split = not (_graphable(pitch_fn) and _graphable(energy_fn))
@@ -93,11 +107,11 @@ def replay(model, x, alpha, pitch_fn, energy_fn, policy, capture, finish):
         wkey = weights_key(model)
         sx = x.clone()
         try:
-            capture(sx, *cap)  # warm-up
+            phase_fn(sx, alpha, *cap, capture=True)  # warm-up
             torch.cuda.synchronize(x.device)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                outs = capture(sx, *cap)
+                outs = phase_fn(sx, alpha, *cap, capture=True)
         except Exception:  # pylint: disable=broad-except
             torch.cuda.synchronize(x.device)
             seen[key] = -1
@@ -117,15 +131,36 @@ def replay(model, x, alpha, pitch_fn, energy_fn, policy, capture, finish):
         main.synchronize()  # the stale replay must finish before its graph is freed
         cache.clear()
         return None
-    phase = list(ent['outs'])
-    t_host = torch.empty((), dtype=phase[TMAX].dtype, pin_memory=True)
-    t_host.copy_(phase[TMAX], non_blocking=True)
+    phase = ent['outs']
+    t_host = torch.empty((), dtype=phase.t_mel.dtype, pin_memory=True)
+    t_host.copy_(phase.t_mel, non_blocking=True)
     t_ready = torch.cuda.Event()
     t_ready.record(main)
-    phase[:3] = [t.clone() for t in phase[:3]]
+    dur, pitch, energy = phase.dur.clone(), phase.pitch.clone(), phase.energy.clone()
     if split:  # the callbacks on the predictors' outputs, then their projections
-        phase[1], phase[2] = pitch_fn(phase[1]), energy_fn(phase[2])
+        pitch, energy = pitch_fn(pitch), energy_fn(energy)
+    phase = phase._replace(dur=dur, pitch=pitch, energy=energy)
+    if split:
         finish(phase)
     t_ready.synchronize()
-    phase[TMAX] = int(t_host)
-    return phase, ent
+    return phase._replace(t_mel=int(t_host)), ent
+
+
+def _nothing() -> None:
+    pass
+
+
+def phoneme_phase(model, phase_fn, finish, policy, x, alpha, pitch_fn, energy_fn, batch=None,
+                  graph=True):
+    """One phoneme phase of `model`: from its graph where `graph` allows one (and x is no
+    shard of a larger batch), else eager.  phase_fn(x, alpha, pitch_fn, energy_fn, batch,
+    capture) is the model's phase, returning a Phase; finish and policy as in `replay`.
+    Returns (Phase, consumed): call consumed() on the decoder's stream once everything that
+    reads phase.h / phase.offsets is queued (the next replay of a graph waits for it)."""
+    r = None
+    if graph and batch is None:
+        r = replay(model, phase_fn, finish, policy, x, alpha, pitch_fn, energy_fn)
+    if r is None:
+        return phase_fn(x, alpha, pitch_fn, energy_fn, batch), _nothing
+    phase, ent = r
+    return phase, lambda: ent['done'].record(torch.cuda.current_stream(x.device))

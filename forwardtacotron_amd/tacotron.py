@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .common_layers import CBHG, Conv1dParams, LinearParams, Packed, _uniform_
+from .common_layers import CBHG, Conv1dParams, LinearParams, Packed, _uniform_, check_device
 from .forward_tacotron import Embedding
 from .text.symbols import phonemes
 
@@ -196,12 +196,8 @@ class Tacotron(nn.Module):
 
     # ---------------------------------------------------------------------------------
     def _check_device(self, x: torch.Tensor) -> None:
-        w = self.encoder.embedding.weight
-        if not w.is_cuda:
-            raise RuntimeError('Tacotron runs on a HIP device only: call .to("cuda") '
-                               '(there is no CPU fallback)')
-        if x.device != w.device:
-            raise RuntimeError(f'input on {x.device}, model on {w.device}')
+        check_device(self.encoder.embedding.weight, x, 'Tacotron',
+                     'call .to("cuda") (there is no CPU fallback)')
 
     def _encode(self, x: torch.Tensor):
         enc = self.encoder(x)

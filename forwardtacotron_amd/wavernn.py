@@ -282,7 +282,8 @@ class WaveRNN(Packed):
     def _model_args(self, a, cond, mel, L):
         """The fields _lib.WaveRNNArgs and _lib.WaveRNNPackedArgs share (bias_row: cond's last
         row, the zero frame); returns the workspace."""
-        for k, v in self.packed_weights()[3].items():
+        *_, rec = self.packed_weights()
+        for k, v in rec.items():
             setattr(a, k, v.data_ptr())
         a.cond, a.mel, a.bias_row = cond.data_ptr(), mel.data_ptr(), cond.size(1) - 1
         a.hop, a.L, a.n_classes, a.mol = self._hop(), L, self.n_classes, int(self.mode == 'MOL')

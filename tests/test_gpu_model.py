@@ -56,6 +56,21 @@ def test_generate_jit_matches_reference(gpu_model):
     check(gpu_model.generate_jit(torch.from_numpy(g['x']).cuda(), alpha=1.1, beta=0.7), g)
 
 
+def test_generate_jit_is_eager_generate_with_scaled_pitch(gpu_model, monkeypatch):
+    """generate_jit(x, alpha, beta) and generate(x, alpha, pitch_function = p * beta) share
+    one run body: with the graph off (generate_jit never uses it) every returned tensor is
+    equal bit for bit."""
+    from forwardtacotron_amd import forward_tacotron as FT
+    x = torch.from_numpy(load_golden('gen_b3')['x']).cuda()
+    alpha, beta = 1.1, 0.7
+    monkeypatch.setattr(FT, 'GRAPH', False)
+    jit = gpu_model.generate_jit(x, alpha, beta)
+    gen = gpu_model.generate(x, alpha, pitch_function=lambda p: p * beta)
+    assert sorted(jit) == sorted(gen) == ['dur', 'energy', 'mel', 'mel_post', 'pitch']
+    for k in gen:
+        assert torch.equal(jit[k], gen[k]), k
+
+
 def test_torchscript_readme_on_hip(gpu_model, synth_sd, tmp_path):
     """reference README.md:149-161 verbatim against this package — a model
     from a checkpoint on the CPU, torch.jit.script, generate_jit on a CPU tensor — computes
