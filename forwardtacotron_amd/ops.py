@@ -591,7 +591,7 @@ def highway(x: torch.Tensor, w12: torch.Tensor, b1: torch.Tensor, b2: torch.Tens
     return y
 
 
-HS_C, HS_NPASS, HS_MAXL = 256, 512, 8  # gemm.hip highway_stack_kernel shape limits
+HS_C, HS_NPASS, HS_MAXL = 256, 512, 8  # highway_stack.hip highway_stack_kernel shape limits
 # The fused stack below FTMI_HS_MIN rows falls back to the per-layer launches.  Round 4
 # moved the default 256 -> 64: at c2 (the prenet's 120 rows) the one launch replaces four
 # skinny GEMMs + four finish launches, c2 2.81 / 2.96 / 2.83 -> 2.80 / 2.81 / 2.80 ms per
@@ -657,7 +657,7 @@ def hs_spread_blocks(M: int, n_out: int = 0) -> int:
     return n if 0 < n <= _num_cus() else 0
 
 
-PANEL_N = 256  # gemm.hip panel_proj_kernel: output columns per panel (LayerNorm width)
+PANEL_N = 256  # highway_stack.hip panel_proj_kernel: output columns per panel (LayerNorm width)
 
 
 def panel_ok(K: int, N: int, ln: bool, split) -> bool:
